@@ -1311,8 +1311,10 @@ class ArrayContains(Expr):
             hit = c.data.to(torch.float64) / 10 ** c.dtype.scale == float(self.value)
         else:
             hit = c.data == self.value
-        out = torch.zeros(n, dtype=torch.bool, device=device)
-        out.scatter_reduce_(0, row, hit, reduce="amax", include_self=True)
+        # uint8 accumulator: the device scatter_reduce_ has no bool kernel
+        out = torch.zeros(n, dtype=torch.uint8, device=device)
+        out.scatter_reduce_(0, row, hit.to(torch.uint8), reduce="amax",
+                            include_self=True)
         return Column(dtypes.bool_, out.to(torch.bool), c.validity)
 
 

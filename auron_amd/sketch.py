@@ -228,8 +228,8 @@ class BloomFilter:
     def put_longs(self, values: torch.Tensor) -> None:
         if values.numel() == 0:
             return
-        idx = self._bit_indexes(values).reshape(-1)
-        mask = torch.zeros(self.m, dtype=torch.bool, device=self.words.device)
+        idx = self._bit_indexes(values).reshape(-1).to(self.words.device)
+        mask =torch.zeros(self.m, dtype=torch.bool, device=self.words.device)
         mask[idx] = True
         weights = torch.tensor(
             [_i64(1 << b) for b in range(64)], dtype=torch.int64,
@@ -243,7 +243,9 @@ class BloomFilter:
         idx = self._bit_indexes(values)  # (n, k)
         word = idx >> 6
         bit = idx & 63
-        hits = (self.words[word] >> bit) & 1
+        # driver-built filter probed with device-resident keys
+        words = self.words.to(values.device)
+        hits = (words[word] >> bit) & 1
         return (hits == 1).all(dim=1)
 
     # Spark sketch serialized form: int32 version, int32 numHashFunctions,
