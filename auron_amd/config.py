@@ -91,6 +91,12 @@ PARTIAL_AGG_SKIPPING_MINROWS = _opt("spark.auron.partialAggSkipping.minRows",
                                     "skipping is never sampled")
 SORT_LIMIT_TOPK = _opt("spark.auron.sort.topK.enable", True, bool,
                        "ORDER BY+LIMIT keeps only the top K rows per batch")
+SORT_EXTERNAL_WIDE_KEYS = _opt("spark.auron.sort.external.wideKeys.enable",
+                               True, bool,
+                               "range-split external sort also for string and "
+                               "decimal128 first keys (off: such sorts stay "
+                               "monolithic and cannot spill)",
+                               env="AURON_SORT_EXTERNAL_WIDE_KEYS")
 EXCHANGE_SAMPLE_ROWS = _opt("spark.auron.rangePartition.sampleRows", 4096, int,
                             "per-rank sample size for range-partition bounds")
 SCAN_CACHE_BYTES = _opt("spark.auron.scan.cache.maxBytes", 0, int,

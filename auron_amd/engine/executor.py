@@ -952,9 +952,13 @@ class Executor:
         batches = self.execute(node.child)
         total = sum(b.num_rows for b in batches)
         _k0 = node.keys[0][0].eval(batches[0]).dtype
-        if (node.limit is None and total > 4 * self.ctx.batch_rows
-                and not _k0.is_string and _k0.code != dtypes.DECIMAL128):
-            return self._exec_sort_external(node, batches, total)
+        if node.limit is None and total > 4 * self.ctx.batch_rows:
+            if not _k0.is_string and _k0.code != dtypes.DECIMAL128:
+                return self._exec_sort_external(node, batches, total)
+            from ..config import SORT_EXTERNAL_WIDE_KEYS
+
+            if AuronConf().get(SORT_EXTERNAL_WIDE_KEYS):
+                return self._exec_sort_external_wide(node, batches, total)
         b = _concat(batches)
         perm = self._sort_permutation(b, node.keys)
         if node.limit is not None:
@@ -1006,6 +1010,81 @@ class Executor:
                 # descending: reverse bucket order (nulls last => last bucket)
                 part = nbuckets - 1 - torch.searchsorted(
                     bounds.flip(0), kd, right=True)
+                if k.validity is not None:
+                    part = torch.where(k.validity, part,
+                                       torch.full_like(part, nbuckets - 1))
+            for i in range(nbuckets):
+                piece = b.filter(part == i)
+                if piece.num_rows:
+                    cur = holders[i].batches()
+                    cur.append(piece)
+                    holders[i].refresh()
+        out: List[RecordBatch] = []
+        for i in range(nbuckets):
+            cur = holders[i].batches()
+            if cur:
+                bb = _concat(cur)
+                perm = self._sort_permutation(bb, node.keys)
+                out.append(bb.gather(perm))
+            holders[i].release()
+        if not out:
+            out = [_concat(batches)]
+        self.ctx.metrics["sort.external_buckets"] = \
+            self.ctx.metrics.get("sort.external_buckets", 0) + nbuckets
+        return out
+
+    def _exec_sort_external_wide(self, node: P.Sort,
+                                 batches: List[RecordBatch],
+                                 total: int) -> List[RecordBatch]:
+        """_exec_sort_external for a string or decimal128 first key: the
+        same range split, with the bounds kept as a Column and rows routed
+        by ops.range_bucket (keys torch.searchsorted cannot compare).
+        Buckets are split by filter (input order kept) and sorted with the
+        stable _sort_permutation, so the concatenated output is row-for-row
+        the monolithic sort's."""
+        device = self.ctx.device
+        key_expr, asc0 = node.keys[0]
+        nbuckets = max(2, (total + 2 * self.ctx.batch_rows - 1)
+                       // (2 * self.ctx.batch_rows))
+        samples = []
+        for b in batches:
+            k = key_expr.eval(b)
+            n = b.num_rows
+            if n:
+                take = min(n, 4096)
+                sel = torch.randperm(n, device=device)[:take]
+                s = k.gather(sel)
+                if s.validity is not None:
+                    s = s.filter(s.validity)
+                samples.append(Column(s.dtype, s.data, None, s.offsets))
+        samp = Column.concat(samples)
+        # string_sort_ranks sorts the unique samples on the host: cap them
+        cap = 65536
+        if len(samp) > cap:
+            samp = samp.gather(torch.randperm(len(samp), device=device)[:cap])
+        m = len(samp)
+        if m == 0:  # no non-null sample at all: zero bounds
+            order = torch.zeros(0, dtype=torch.int64, device=device)
+        elif samp.dtype.is_string:
+            order = torch.argsort(ops.string_sort_ranks(samp), stable=True)
+        else:
+            o1 = torch.argsort(samp.data[:, 0] ^ (-(1 << 63)), stable=True)
+            order = o1[torch.argsort(samp.data[:, 1][o1], stable=True)]
+        qi = (torch.linspace(0, 1, nbuckets + 1, device=device,
+                             dtype=torch.float64)[1:-1]
+              * max(m - 1, 0)).round().to(torch.int64)
+        bounds = samp.gather(order[qi] if m else order)
+        holders = [self.ctx.memmgr.register(f"sort-bucket-{i}", [])
+                   for i in range(nbuckets)]
+        for b in batches:
+            k = key_expr.eval(b)
+            if asc0:
+                part = ops.range_bucket(k, bounds, right=False)
+                if k.validity is not None:  # nulls first under asc
+                    part = torch.where(k.validity, part, torch.zeros_like(part))
+            else:
+                # descending: reverse bucket order (nulls last => last bucket)
+                part = nbuckets - 1 - ops.range_bucket(k, bounds, right=True)
                 if k.validity is not None:
                     part = torch.where(k.validity, part,
                                        torch.full_like(part, nbuckets - 1))
@@ -1185,13 +1264,9 @@ class Executor:
             allsamp = sorted(v for g in gathered if g for v in g if v is not None)
             bounds = [allsamp[len(allsamp) * (d + 1) // W]
                       for d in range(W - 1)] if allsamp else [""] * (W - 1)
-            from .. import strings as S
-
-            part = torch.zeros(n, dtype=torch.int64, device=device)
-            for bd in bounds:
-                gt = ~S.compare(key, Column.from_pylist([bd] * n, dtypes.string,
-                                                        str(device)), "<=")
-                part += gt.to(torch.int64)
+            part = ops.range_bucket(
+                key, Column.from_pylist(bounds, dtypes.string, str(device)),
+                right=False)
             if key.validity is not None:
                 part = torch.where(key.validity, part, torch.zeros_like(part))
             dest = [b.filter(part == d) for d in range(W)]

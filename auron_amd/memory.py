@@ -46,6 +46,7 @@ class BatchHolder:
         self._spill_file: Optional[str] = None
         self.bytes = sum(_batch_bytes(b) for b in batches)
         self.device = batches[0].device if batches else torch.device("cpu")
+        self._device_known = bool(batches)
         self.last_touch = time.monotonic()
 
     @property
@@ -60,6 +61,11 @@ class BatchHolder:
         """Re-account after the caller mutated the resident batch list
         (update_mem_used analogue); may trigger spills elsewhere."""
         if self._batches is not None:
+            if not self._device_known and self._batches:
+                # registered empty (device unknown then): adopt the device
+                # of the first payload so a restore lands where it was
+                self.device = self._batches[0].device
+                self._device_known = True
             self.bytes = sum(_batch_bytes(b) for b in self._batches)
             self.last_touch = time.monotonic()
             self.mgr.reserve(0)

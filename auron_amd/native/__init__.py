@@ -81,6 +81,10 @@ def _try_load():
     lib.au_expr_exec.restype = ctypes.c_int
     lib.au_part_hist.argtypes = [c, i64, i32, c, c]
     lib.au_part_scatter.argtypes = [c, i64, c, c, c, c]
+    lib.au_range_bucket_str.argtypes = [c, c, i64, c, c, i32, ctypes.c_int, c, c]
+    lib.au_range_bucket_i128.argtypes = [c, i64, c, i32, ctypes.c_int, c, c]
+    for f in ("au_range_bucket_str", "au_range_bucket_i128"):
+        getattr(lib, f).restype = ctypes.c_int
     for f in ("au_murmur3", "au_group_ids", "au_join_build", "au_join_count",
               "au_join_fill", "au_pmod", "au_part_hist", "au_part_scatter"):
         getattr(lib, f).restype = ctypes.c_int

@@ -387,6 +387,136 @@ def string_sort_ranks(c: Column) -> torch.Tensor:
     return rank_t[gids]
 
 
+# ============================================================= range bucket
+_MIN64 = -(1 << 63)
+
+
+def _bytes_cmp_sign(a_data, a_start, a_len, b_data, b_start, b_len,
+                    chunk: int = 64) -> torch.Tensor:
+    """Row-wise sign of the unsigned-byte lexicographic compare a[i] vs b[i]
+    (-1 / 0 / +1, int64); a proper prefix sorts first. Exact for any length:
+    the padded compare walks `chunk` byte columns at a time over the rows
+    still undecided (padding is -1, below every byte)."""
+    n = a_start.numel()
+    device = a_start.device
+    sign = torch.zeros(n, dtype=torch.int64, device=device)
+    if n == 0:
+        return sign
+    if a_data.numel() == 0:
+        a_data = torch.zeros(1, dtype=torch.uint8, device=device)
+    if b_data.numel() == 0:
+        b_data = torch.zeros(1, dtype=torch.uint8, device=device)
+    width = int(torch.maximum(a_len.max(), b_len.max()).item())
+    und = torch.arange(n, dtype=torch.int64, device=device)
+    pos = torch.arange(chunk, dtype=torch.int64, device=device)
+    pad = torch.full((), -1, dtype=torch.int16, device=device)
+    c = 0
+    while c < width and und.numel():
+        p = (c + pos)[None, :]
+
+        def _pad(data, start, ln):
+            idx = (start[und, None] + p).clamp(0, data.numel() - 1)
+            return torch.where(p < ln[und, None], data[idx].to(torch.int16), pad)
+
+        av = _pad(a_data, a_start, a_len)
+        bv = _pad(b_data, b_start, b_len)
+        neq = av != bv
+        anyd = neq.any(1)
+        first = neq.to(torch.int8).argmax(1, keepdim=True)
+        d = (av.gather(1, first) - bv.gather(1, first)).squeeze(1).sign()
+        sign[und[anyd]] = d[anyd].to(torch.int64)
+        und = und[~anyd]
+        c += chunk
+    return sign
+
+
+def range_bucket_ref(key: Column, bounds: Column, right: bool = False) -> torch.Tensor:
+    """Oracle for range_bucket (pure torch, exact — no padded-width
+    truncation): torch.searchsorted(bounds, key, right=right) semantics
+    for string and decimal128 keys."""
+    device = key.device
+    n = len(key)
+    nb = len(bounds)
+    if key.dtype.is_string:
+        k_start = key.offsets[:-1]
+        k_len = key.offsets[1:] - k_start
+        b_start = bounds.offsets[:-1]
+        b_len = bounds.offsets[1:] - b_start
+        lo = torch.zeros(n, dtype=torch.int64, device=device)
+        hi = torch.full((n,), nb, dtype=torch.int64, device=device)
+        # binary search vectorised over rows: the interval at least halves
+        # per step, so bit_length(nb) steps close every row
+        for _ in range(nb.bit_length()):
+            active = lo < hi
+            mid = ((lo + hi) >> 1).clamp(max=max(nb - 1, 0))
+            c = _bytes_cmp_sign(bounds.data, b_start[mid], b_len[mid],
+                                key.data, k_start, k_len)
+            go = (c <= 0) if right else (c < 0)
+            lo = torch.where(active & go, mid + 1, lo)
+            hi = torch.where(active & ~go, mid, hi)
+        return lo
+    assert key.dtype.code == dtypes.DECIMAL128
+    out = torch.zeros(n, dtype=torch.int64, device=device)
+    lo_u = key.data[:, 0] ^ _MIN64
+    hi_s = key.data[:, 1]
+    for j in range(nb):
+        bl = bounds.data[j, 0] ^ _MIN64
+        bh = bounds.data[j, 1]
+        gt = (hi_s > bh) | ((hi_s == bh) & (lo_u > bl))
+        if right:
+            gt = gt | ((hi_s == bh) & (lo_u == bl))
+        out += gt.to(torch.int64)
+    return out
+
+
+def range_bucket(key: Column, bounds: Column, right: bool = False) -> torch.Tensor:
+    """Range bucket of every row of `key` against the ascending, non-null
+    `bounds` (-> int64 [len(key)] on the key's device), with the semantics
+    of torch.searchsorted(bounds, key, right=right): the number of bounds
+    strictly less than the row, or `<=` the row when `right`.
+
+    Strings order by unsigned UTF-8 bytes (a proper prefix first);
+    decimal128 by its full 128-bit value. Null rows get an arbitrary
+    bucket — the caller overwrites them."""
+    assert bounds.validity is None or bool(bounds.validity.all()), \
+        "range_bucket: bounds must be non-null"
+    device = key.device
+    wide = key.dtype.is_string or key.dtype.code == dtypes.DECIMAL128
+    if not wide:
+        assert not bounds.dtype.is_string and bounds.dtype.code != dtypes.DECIMAL128, \
+            f"range_bucket: {key.dtype.name} key vs {bounds.dtype.name} bounds"
+        kd, bd = key.data, bounds.data.to(device)
+        if kd.dtype == torch.bool:
+            kd = kd.to(torch.int8)
+        if bd.dtype != kd.dtype:
+            t = torch.promote_types(kd.dtype, bd.dtype)
+            kd, bd = kd.to(t), bd.to(t)
+        return torch.searchsorted(bd, kd, right=right)
+    assert bounds.dtype.code == key.dtype.code, \
+        f"range_bucket: {key.dtype.name} key vs {bounds.dtype.name} bounds"
+    bounds = bounds.to(device)
+    if not _use_native(device):
+        return range_bucket_ref(key, bounds, right)
+    lib = native.lib()
+    n = len(key)
+    nb = len(bounds)
+    out = torch.empty(n, dtype=torch.int32, device=device)
+    sp = native.stream_ptr(device)
+    if key.dtype.is_string:
+        kdata, koff = key.data.contiguous(), key.offsets.contiguous()
+        bdata, boff = bounds.data.contiguous(), bounds.offsets.contiguous()
+        rc = lib.au_range_bucket_str(kdata.data_ptr(), koff.data_ptr(), n,
+                                     bdata.data_ptr(), boff.data_ptr(), nb,
+                                     int(bool(right)), out.data_ptr(), sp)
+        native.check(rc, "au_range_bucket_str")
+    else:
+        kdata, bdata = key.data.contiguous(), bounds.data.contiguous()
+        rc = lib.au_range_bucket_i128(kdata.data_ptr(), n, bdata.data_ptr(),
+                                      nb, int(bool(right)), out.data_ptr(), sp)
+        native.check(rc, "au_range_bucket_i128")
+    return out.to(torch.int64)
+
+
 # ================================================================ partition
 def _normalize_hash_col(c: Column) -> Column:
     """Promote key columns to a canonical width before hashing: murmur3
