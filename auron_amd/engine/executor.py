@@ -2208,6 +2208,11 @@ class Executor:
         sb._eval_memo = {}  # CSE scope; sb is operator-local, dies with it
         names = list(sb.names)
         cols = list(sb.columns)
+        # RANGE frame with explicit bounds: resolve (a, b) once per node
+        value_frame = None
+        if (node.frame == "range"
+                and not (node.frame_lo is None and node.frame_hi == 0)):
+            value_frame = self._range_frame_bounds(node, sb, seg, seg_start)
         for al in node.functions:
             wf: WindowFunc = al.expr  # type: ignore
             if wf.fn == "row_number":
@@ -2259,7 +2264,9 @@ class Executor:
                 bounded = (node.frame == "rows"
                            and not (node.frame_lo is None
                                     and node.frame_hi == 0))
-                if bounded and n:
+                if value_frame is not None:
+                    out = self._frame_aggregate(wf.fn, val, *value_frame)
+                elif bounded and n:
                     out = self._bounded_rows_window(
                         wf.fn, val, seg, seg_start,
                         node.frame_lo, node.frame_hi)
@@ -2330,7 +2337,13 @@ class Executor:
                                  torch.where(pos_in_seg < cut, lo, hi))
             elif wf.fn in ("first_value", "last_value", "nth_value"):
                 val = wf.arg.eval(sb)
-                if wf.fn == "first_value":
+                if value_frame is not None and wf.fn != "nth_value":
+                    fa, fb, fempty = value_frame
+                    at = fa if wf.fn == "first_value" else fb
+                    out = val.gather(
+                        torch.where(fempty, torch.full_like(at, -1), at),
+                        may_have_negative=True)
+                elif wf.fn == "first_value":
                     out = val.gather(seg_start[seg]) if n else val
                 elif wf.fn == "last_value":
                     # frame unbounded preceding..current: ROWS -> current row;
@@ -2384,11 +2397,155 @@ class Executor:
                           torch.tensor([n - 1], dtype=torch.int64, device=device)])
         return pend[pg]
 
+    def _range_frame_bounds(self, node, sb, seg, seg_start):
+        """RANGE BETWEEN <lo> AND <hi> with explicit bounds (Spark's
+        semantics) -> per-row inclusive frame (a, b, empty) over the sorted
+        rows, or None for an empty input.
+
+        CURRENT ROW is the whole peer group; a value offset compares the
+        single ORDER BY key (k+lo <= key <= k+hi ascending, k-lo >= key >=
+        k-hi descending; integer k±offset saturates). Rows whose key is
+        NULL — or NaN for float keys — are special: their offset/current
+        bounds resolve to their own peer group, and an ordinary row's offset
+        bound never reaches them. Unbounded is the partition edge."""
+        lo, hi = node.frame_lo, node.frame_hi
+        by_value = ((lo is not None and lo != 0) or (hi != "U" and hi != 0))
+        key = None
+        if by_value:
+            if len(node.order_by) != 1:
+                raise ValueError(
+                    "a RANGE frame with a value offset needs exactly one "
+                    f"ORDER BY key, got {len(node.order_by)}")
+            key = node.order_by[0][0].eval(sb)
+            kdt = key.dtype
+            if not (kdt.is_integer or kdt.is_float or kdt.code in (
+                    dtypes.DATE32, dtypes.TIMESTAMP, dtypes.DECIMAL64)):
+                raise NotImplementedError(
+                    f"RANGE frame value offsets over a {kdt.name} key")
+            want = float if kdt.is_float else int
+            for v in (lo, hi):
+                if v is not None and v != "U" and (
+                        isinstance(v, bool) or not isinstance(v, (int, float))
+                        or (want is int and not isinstance(v, int))):
+                    raise ValueError(
+                        f"RANGE frame bound {v!r} does not fit a {kdt.name} "
+                        "key")
+        n = seg.numel()
+        if n == 0:
+            return None
+        device = seg.device
+        idx = torch.arange(n, dtype=torch.int64, device=device)
+        first = seg_start[seg]
+        seg_last = torch.cat([seg_start[1:] - 1,
+                              torch.tensor([n - 1], dtype=torch.int64,
+                                           device=device)])
+        last = seg_last[seg]
+        # peer groups (NaN keys are peers of each other, as NULLs are)
+        peer_first = torch.zeros(n, dtype=torch.bool, device=device)
+        if node.order_by and n > 1:
+            sp = torch.ones(n - 1, dtype=torch.bool, device=device)
+            for k, _ in node.order_by:
+                sp = sp & self._col_eq_adjacent(k.eval(sb), nan_equal=True)
+            peer_first[1:] = ~sp
+        peer_first[seg_start] = True
+        pstart = torch.nonzero(peer_first, as_tuple=False).flatten()
+        pend = torch.cat([pstart[1:] - 1,
+                          torch.tensor([n - 1], dtype=torch.int64,
+                                       device=device)])
+        pg = torch.cumsum(peer_first.to(torch.int64), 0) - 1
+        a, b = pstart[pg], pend[pg]
+        if by_value:
+            asc = node.order_by[0][1]
+            if key.dtype.is_float:
+                kd = key.data.to(torch.float64)
+                special = torch.isnan(kd)
+            else:
+                kd = key.data.to(torch.int64)
+                special = torch.zeros(n, dtype=torch.bool, device=device)
+            if key.validity is not None:
+                special = special | ~key.validity
+            # ordinary keys sit contiguously inside each partition (NULLs
+            # and NaNs sort to its ends): per-partition window [slo, shi]
+            ordinary = ~special
+            nseg = seg_start.numel()
+            slo = torch.full((nseg,), n, dtype=torch.int64, device=device)
+            shi = torch.full((nseg,), -1, dtype=torch.int64, device=device)
+            slo.scatter_reduce_(0, seg[ordinary], idx[ordinary], "amin")
+            shi.scatter_reduce_(0, seg[ordinary], idx[ordinary], "amax")
+            # (a partition without ordinary keys keeps the empty [n, -1])
+            ka, kb = ops.window_range_bounds(kd, slo[seg], shi[seg], lo, hi,
+                                             descending=not asc)
+            a = torch.where(special, a, ka)
+            b = torch.where(special, b, kb)
+            self.ctx.metrics["window.range_frame_rows"] = \
+                self.ctx.metrics.get("window.range_frame_rows", 0) + n
+        if lo is None:
+            a = first
+        if hi == "U":
+            b = last
+        return a, b, a > b
+
+    def _frame_aggregate(self, fn: str, val: Column, a: torch.Tensor,
+                         b: torch.Tensor, empty: torch.Tensor) -> Column:
+        """sum/avg/count/min/max over per-row inclusive frames [a, b]
+        (`empty` marks a > b): prefix-sum differences for sum/avg/count,
+        the frame min/max primitive for min/max. Nulls are skipped; a
+        frame with no valid value gives NULL (count 0)."""
+        device = a.device
+        n = a.numel()
+        valid = val.validity if val.validity is not None else \
+            torch.ones(n, dtype=torch.bool, device=device)
+        C = torch.cumsum(valid.to(torch.int64), 0)
+
+        def rng(P):
+            hi_v = P[b.clamp(min=0)]
+            lo_i = a - 1
+            lo_v = torch.where(lo_i >= 0, P[lo_i.clamp(min=0)],
+                               torch.zeros((), dtype=P.dtype, device=device))
+            out = hi_v - lo_v
+            return torch.where(empty, torch.zeros_like(out), out)
+
+        cnt = rng(C)
+        if fn == "count":
+            return Column(dtypes.int64, cnt)
+        if fn in ("sum", "avg"):
+            vd = val.data
+            if vd.dtype not in (torch.float64, torch.float32):
+                vd = vd.to(torch.int64)
+            x = torch.where(valid, vd, torch.zeros_like(vd))
+            s = rng(torch.cumsum(x, 0))
+            if fn == "avg":
+                data = s.to(torch.float64) / cnt.clamp(min=1).to(torch.float64)
+                if val.dtype.code == dtypes.DECIMAL64:
+                    data = data / (10.0 ** val.dtype.scale)
+                return Column(dtypes.float64, data,
+                              compact_validity(cnt > 0))
+            out_dt = val.dtype if val.dtype.code == dtypes.DECIMAL64 else (
+                dtypes.float64 if val.dtype.is_float else dtypes.int64)
+            return Column(out_dt, s.to(out_dt.torch_dtype),
+                          compact_validity(cnt > 0))
+        assert fn in ("min", "max"), fn
+        vd = val.data
+        work = vd.to(torch.float64) if vd.dtype.is_floating_point \
+            else vd.to(torch.int64)
+        if work.dtype == torch.int64:
+            fill = torch.iinfo(torch.int64).max if fn == "min" \
+                else torch.iinfo(torch.int64).min
+        else:
+            fill = float("inf") if fn == "min" else float("-inf")
+        x = torch.where(valid, work, torch.full_like(work, fill))
+        # an empty frame (a > b) yields the identity; cnt == 0 makes it NULL
+        m = ops.window_frame_minmax(x, a, b, fn)
+        self.ctx.metrics["window.frame_minmax_rows"] = \
+            self.ctx.metrics.get("window.frame_minmax_rows", 0) + n
+        return Column(val.dtype, m.to(vd.dtype), compact_validity(cnt > 0))
+
     def _bounded_rows_window(self, fn: str, val: Column, seg: torch.Tensor,
                              seg_start: torch.Tensor, lo, hi) -> Column:
         """Explicit ROWS BETWEEN bounds (window_exec.rs frame processors):
         sum/avg/count via segment-clamped prefix sums; min/max via a
-        shifted-compare chain over the (bounded) span."""
+        shifted-compare chain over a short bounded span, else via the
+        frame min/max primitive (unbounded side or span >= 1024)."""
         device = seg.device
         n = seg.numel()
         counts = torch.bincount(seg, minlength=int(seg.max().item()) + 1 if n else 1)
@@ -2401,38 +2558,11 @@ class Executor:
         valid = val.validity if val.validity is not None else \
             torch.ones(n, dtype=torch.bool, device=device)
         if fn in ("sum", "avg", "count"):
-            vd = val.data
-            if vd.dtype not in (torch.float64, torch.float32):
-                vd = vd.to(torch.int64)
-            x = torch.where(valid, vd, torch.zeros_like(vd))
-            S = torch.cumsum(x, 0)
-            C = torch.cumsum(valid.to(torch.int64), 0)
-
-            def rng(P, dt):
-                hi_v = P[b.clamp(min=0)]
-                lo_i = a - 1
-                lo_v = torch.where(lo_i >= 0, P[lo_i.clamp(min=0)],
-                                   torch.zeros((), dtype=P.dtype, device=device))
-                out = hi_v - lo_v
-                return torch.where(empty, torch.zeros_like(out), out)
-
-            cnt = rng(C, torch.int64)
-            if fn == "count":
-                return Column(dtypes.int64, cnt)
-            s = rng(S, vd.dtype)
-            if fn == "avg":
-                data = s.to(torch.float64) / cnt.clamp(min=1).to(torch.float64)
-                if val.dtype.code == dtypes.DECIMAL64:
-                    data = data / (10.0 ** val.dtype.scale)
-                return Column(dtypes.float64, data,
-                              compact_validity(cnt > 0))
-            out_dt = val.dtype if val.dtype.code == dtypes.DECIMAL64 else (
-                dtypes.float64 if val.dtype.is_float else dtypes.int64)
-            return Column(out_dt, s.to(out_dt.torch_dtype),
-                          compact_validity(cnt > 0))
+            return self._frame_aggregate(fn, val, a, b, empty)
+        if not (isinstance(lo, int) and isinstance(hi, int)
+                and hi - lo < 1024):
+            return self._frame_aggregate(fn, val, a, b, empty)
         # min/max: chain of shifted comparisons over the span
-        assert isinstance(lo, int) and isinstance(hi, int) and hi - lo < 1024, \
-            "bounded ROWS min/max supports spans < 1024"
         cmp = torch.minimum if fn == "min" else torch.maximum
         acc = None
         acc_ok = torch.zeros(n, dtype=torch.bool, device=device)
@@ -2512,8 +2642,9 @@ class Executor:
             return Column(dtypes.int64, run, validity)
         return Column(dtypes.float64, run, validity)
 
-    def _col_eq_adjacent(self, c: Column) -> torch.Tensor:
-        """eq mask between row i and i-1, for rows 1..n-1 (null==null)."""
+    def _col_eq_adjacent(self, c: Column, nan_equal: bool = False) -> torch.Tensor:
+        """eq mask between row i and i-1, for rows 1..n-1 (null==null;
+        NaN==NaN only when `nan_equal`)."""
         n = len(c)
         if n <= 1:
             return torch.zeros(0, dtype=torch.bool, device=c.device)
@@ -2525,6 +2656,8 @@ class Executor:
             eq = S.compare(a, bcol, "==")
         else:
             eq = a.data == bcol.data
+            if nan_equal and c.dtype.is_float:
+                eq = eq | (torch.isnan(a.data) & torch.isnan(bcol.data))
         av = a.validity if a.validity is not None else torch.ones(n - 1, dtype=torch.bool, device=c.device)
         bv = bcol.validity if bcol.validity is not None else torch.ones(n - 1, dtype=torch.bool, device=c.device)
         return (eq & av & bv) | (~av & ~bv)

@@ -85,6 +85,20 @@ def _try_load():
     lib.au_range_bucket_i128.argtypes = [c, i64, c, i32, ctypes.c_int, c, c]
     for f in ("au_range_bucket_str", "au_range_bucket_i128"):
         getattr(lib, f).restype = ctypes.c_int
+    f64 = ctypes.c_double
+    lib.au_window_range_bounds_i64.argtypes = [c, c, c, i64, i64, i64,
+                                               ctypes.c_int, c, c, c]
+    lib.au_window_range_bounds_f64.argtypes = [c, c, c, i64, f64, f64,
+                                               ctypes.c_int, c, c, c]
+    lib.au_window_frame_minmax_i64.argtypes = [c, i64, c, i64, c, c, i64,
+                                               ctypes.c_int, c, c]
+    lib.au_window_frame_minmax_f64.argtypes = [c, i64, c, i64, c, c, i64,
+                                               ctypes.c_int, c, c]
+    lib.au_window_pyramid_size.argtypes = [i64]
+    lib.au_window_pyramid_size.restype = i64
+    for f in ("au_window_range_bounds_i64", "au_window_range_bounds_f64",
+              "au_window_frame_minmax_i64", "au_window_frame_minmax_f64"):
+        getattr(lib, f).restype = ctypes.c_int
     for f in ("au_murmur3", "au_group_ids", "au_join_build", "au_join_count",
               "au_join_fill", "au_pmod", "au_part_hist", "au_part_scatter"):
         getattr(lib, f).restype = ctypes.c_int

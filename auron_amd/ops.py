@@ -517,6 +517,194 @@ def range_bucket(key: Column, bounds: Column, right: bool = False) -> torch.Tens
     return out.to(torch.int64)
 
 
+# ============================================================ window frames
+_MAX64 = (1 << 63) - 1
+
+
+def _sat_add(k: torch.Tensor, d: int) -> torch.Tensor:
+    """k + d over int64, saturating at the int64 limits (never wraps)."""
+    d = int(d)
+    assert -_MAX64 <= d <= _MAX64, "window offset out of int64 range"
+    s = k + d  # wraps
+    if d > 0:
+        return torch.where(s < k, torch.full_like(k, _MAX64), s)
+    if d < 0:
+        return torch.where(s > k, torch.full_like(k, _MIN64), s)
+    return s
+
+
+def _window_bounds_args(key, slo, shi, lo, hi):
+    assert key.dtype in (torch.int64, torch.float64), \
+        f"window_range_bounds: int64 or float64 keys, got {key.dtype}"
+    assert slo.dtype == torch.int64 and shi.dtype == torch.int64
+    assert key.numel() == slo.numel() == shi.numel()
+    is_int = key.dtype == torch.int64
+    conv = int if is_int else float
+    lo_v = conv(0) if lo is None else conv(lo)
+    hi_v = conv(0) if hi == "U" else conv(hi)
+    if is_int:
+        assert -_MAX64 <= lo_v <= _MAX64 and -_MAX64 <= hi_v <= _MAX64, \
+            "window offset out of int64 range"
+    return lo_v, hi_v
+
+
+def window_range_bounds_ref(key: torch.Tensor, slo: torch.Tensor,
+                            shi: torch.Tensor, lo, hi,
+                            descending: bool = False):
+    """Oracle for window_range_bounds (pure torch): the same two binary
+    searches, vectorised over rows."""
+    lo_v, hi_v = _window_bounds_args(key, slo, shi, lo, hi)
+    n = key.numel()
+    is_int = key.dtype == torch.int64
+    w0 = slo.clamp(min=0)
+    w1 = shi.clamp(max=n - 1)
+    if n == 0:
+        return w0.clone(), w1.clone()
+
+    def target(off):
+        if is_int:
+            return _sat_add(key, -off if descending else off)
+        return key - off if descending else key + off
+
+    steps = max(int((w1 - w0).max().item()) + 1, 1).bit_length()
+
+    def search(inside, first):
+        # first=True : first index whose key is inside  (inside is a suffix)
+        # first=False: one past the last inside index   (inside is a prefix)
+        l, h = w0.clone(), w1 + 1
+        for _ in range(steps):
+            active = l < h
+            mid = (l + ((h - l) >> 1)).clamp(0, n - 1)
+            ins = inside(key[mid])
+            go_left = ins if first else ~ins
+            h = torch.where(active & go_left, mid, h)
+            l = torch.where(active & ~go_left, mid + 1, l)
+        return l
+
+    if lo is None:
+        a = w0.clone()
+    else:
+        t = target(lo_v)
+        a = search((lambda v: v <= t) if descending else (lambda v: v >= t),
+                   True)
+    if hi == "U":
+        b = w1.clone()
+    else:
+        t = target(hi_v)
+        b = search((lambda v: v >= t) if descending else (lambda v: v <= t),
+                   False) - 1
+    return a, b
+
+
+def window_range_bounds(key: torch.Tensor, slo: torch.Tensor,
+                        shi: torch.Tensor, lo, hi, descending: bool = False):
+    """RANGE-frame resolution by key value -> (a, b), int64 [n] each.
+
+    `key` (int64 or float64) is sorted so that inside every row's inclusive
+    index window [slo[i], shi[i]] the keys are monotone — non-decreasing,
+    or non-increasing when `descending` — with no null or NaN in it.
+    `lo` / `hi` are signed offsets in the key domain (preceding < 0), or
+    None (lo) / "U" (hi) for unbounded, which resolve to the window edge.
+    With k = key[i]:
+      a[i] = first j in the window with key[j] >= k+lo   (desc: <= k-lo)
+      b[i] = last  j in the window with key[j] <= k+hi   (desc: >= k-hi)
+    and a[i] = shi[i]+1 / b[i] = slo[i]-1 when no key qualifies, so
+    a > b marks an empty frame. int64 k±offset saturates; float64 is IEEE."""
+    lo_v, hi_v = _window_bounds_args(key, slo, shi, lo, hi)
+    device = key.device
+    if not _use_native(device):
+        return window_range_bounds_ref(key, slo, shi, lo, hi, descending)
+    lib = native.lib()
+    n = key.numel()
+    key, slo, shi = key.contiguous(), slo.contiguous(), shi.contiguous()
+    a = torch.empty(n, dtype=torch.int64, device=device)
+    b = torch.empty(n, dtype=torch.int64, device=device)
+    flags = ((1 if lo is None else 0) | (2 if hi == "U" else 0)
+             | (4 if descending else 0))
+    fn = (lib.au_window_range_bounds_i64 if key.dtype == torch.int64
+          else lib.au_window_range_bounds_f64)
+    rc = fn(key.data_ptr(), slo.data_ptr(), shi.data_ptr(), n, lo_v, hi_v,
+            flags, a.data_ptr(), b.data_ptr(), native.stream_ptr(device))
+    native.check(rc, "au_window_range_bounds")
+    return a, b
+
+
+def _window_minmax_args(x, a, b, op):
+    assert op in ("min", "max"), op
+    assert x.dtype in (torch.int64, torch.float64), \
+        f"window_frame_minmax: int64 or float64 values, got {x.dtype}"
+    assert a.dtype == torch.int64 and b.dtype == torch.int64
+    assert a.numel() == b.numel()
+    if x.dtype == torch.int64:
+        return _MIN64 if op == "max" else _MAX64
+    return float("-inf") if op == "max" else float("inf")
+
+
+def window_frame_minmax_ref(x: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
+                            op: str) -> torch.Tensor:
+    """Oracle for window_frame_minmax (pure torch): doubling sparse table,
+    two overlapping power-of-two blocks per query."""
+    ident = _window_minmax_args(x, a, b, op)
+    n = x.numel()
+    combine = torch.minimum if op == "min" else torch.maximum
+    out = torch.full((a.numel(),), ident, dtype=x.dtype, device=x.device)
+    lo = a.clamp(min=0)
+    hi = b.clamp(max=n - 1)
+    ln = hi - lo + 1
+    if a.numel() == 0 or n == 0 or int(ln.max().item()) <= 0:
+        return out
+    level = x
+    k = 0
+    maxlen = int(ln.max().item())
+    while True:
+        w = 1 << k
+        # rows whose frame length is in [2^k, 2^(k+1))
+        sel = (ln >= w) & (ln < 2 * w)
+        if bool(sel.any()):
+            out[sel] = combine(level[lo[sel]], level[hi[sel] - w + 1])
+        if 2 * w > maxlen:
+            break
+        # level[i] = op(x[i .. i+2w-1]); the tail keeps shorter blocks,
+        # which no query of that length can address
+        nxt = level.clone()
+        nxt[:n - w] = combine(level[:n - w], level[w:])
+        level = nxt
+        k += 1
+    return out
+
+
+def window_frame_minmax(x: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
+                        op: str) -> torch.Tensor:
+    """Per-row min or max of x[a[i] .. b[i]] (inclusive; int64 or float64 x).
+
+    Nulls must already be replaced by the identity (int64 max/min, ±inf);
+    an empty frame (a > b) yields the identity. Floating NaN propagates,
+    as with torch.minimum / torch.maximum. The native path builds a 64-ary
+    min/max pyramid once, so the cost per row does not grow with the frame
+    width."""
+    _window_minmax_args(x, a, b, op)
+    device = x.device
+    if not _use_native(device):
+        return window_frame_minmax_ref(x, a, b, op)
+    lib = native.lib()
+    n = x.numel()
+    rows = a.numel()
+    out = torch.empty(rows, dtype=x.dtype, device=device)
+    if rows == 0:
+        return out
+    assert n > 0, "window_frame_minmax: frames over an empty array"
+    x, a, b = x.contiguous(), a.contiguous(), b.contiguous()
+    pyr_len = int(lib.au_window_pyramid_size(n))  # levels above x
+    pyr = torch.empty(max(pyr_len, 1), dtype=x.dtype, device=device)
+    fn = (lib.au_window_frame_minmax_i64 if x.dtype == torch.int64
+          else lib.au_window_frame_minmax_f64)
+    rc = fn(x.data_ptr(), n, pyr.data_ptr(), pyr_len, a.data_ptr(),
+            b.data_ptr(), rows, int(op == "max"), out.data_ptr(),
+            native.stream_ptr(device))
+    native.check(rc, "au_window_frame_minmax")
+    return out
+
+
 # ================================================================ partition
 def _normalize_hash_col(c: Column) -> Column:
     """Promote key columns to a canonical width before hashing: murmur3

@@ -197,14 +197,27 @@ class Window(PlanNode):
 
     `frame` applies to running aggregates when order_by is present:
     "range" (Spark's default — UNBOUNDED PRECEDING..CURRENT ROW with
-    peer rows sharing the frame end) or "rows"."""
+    peer rows sharing the frame end) or "rows".
+
+    `frame_lo` / `frame_hi` bound the frame of sum/avg/count/min/max (and,
+    for RANGE, first_value/last_value). ROWS offsets count rows. RANGE
+    offsets are in the domain of the single ORDER BY key — int for the int
+    family, date32 (days), timestamp (microseconds) and decimal64
+    (unscaled value), float for float keys — and select the partition
+    rows with k+lo <= key <= k+hi (descending: k-lo >= key >= k-hi);
+    integer k±offset saturates at the int64 limits. For RANGE, 0 (CURRENT
+    ROW) is the whole peer group, and rows with a NULL (or NaN) key frame
+    only their own peer group on an offset/current side. An empty frame
+    gives count 0 and NULL otherwise."""
     child: PlanNode
     partition_by: List[Expr]
     order_by: List[Tuple[Expr, bool]]
     functions: List[Aliased]  # WindowFunc exprs aliased to output names
     frame: str = "range"
-    # explicit ROWS bounds: None = unbounded preceding, "U" = unbounded
-    # following, int = signed row offset; defaults = the SQL default frame
+    # explicit bounds: None = unbounded preceding, "U" = unbounded
+    # following, number = signed offset (preceding < 0; int for ROWS and
+    # integer-domain RANGE keys, float for float RANGE keys);
+    # defaults = the SQL default frame
     frame_lo: object = None
     frame_hi: object = 0
 

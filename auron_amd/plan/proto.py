@@ -501,6 +501,11 @@ def encode_plan(node: P.PlanNode) -> bytes:
                 for a in node.functions:
                     write_len(b, 4, _enc_aliased(a))
                 write_str(b, 5, node.frame)
+                # bounds only when they differ from the default frame, so
+                # default-frame plans keep their encoding
+                if not (node.frame_lo is None and node.frame_hi == 0):
+                    _enc_frame_bound(b, 6, node.frame_lo)
+                    _enc_frame_bound(b, 9, node.frame_hi)
 
             child(o, 22, _msg(m))
         elif isinstance(node, P.Generate):
@@ -608,7 +613,9 @@ def decode_plan(buf: bytes) -> P.PlanNode:
         return P.Window(plan(), [decode_expr(x) for x in m.get(2, [])],
                         [_dec_sortkey(x) for x in m.get(3, [])],
                         [_dec_aliased(x) for x in m.get(4, [])],
-                        strv(5, "range"))
+                        strv(5, "range"),
+                        _dec_frame_bound(m, 6, None),
+                        _dec_frame_bound(m, 9, 0))
     if tag == 23:
         return P.Generate(plan(), strv(2),
                           [decode_expr(x) for x in m.get(3, [])])
@@ -620,6 +627,41 @@ def decode_plan(buf: bytes) -> P.PlanNode:
     if tag == 27:
         return P.OrcSink(plan(), strv(2))
     raise ValueError(f"unknown PhysicalPlanNode tag {tag}")
+
+
+# FrameBoundKind (auron.proto); fields kind, int value, double value sit at
+# consecutive tags
+_FB_UNBOUNDED_PRECEDING, _FB_UNBOUNDED_FOLLOWING = 1, 2
+_FB_OFFSET_INT, _FB_OFFSET_DOUBLE = 3, 4
+
+
+def _enc_frame_bound(b: bytearray, tag: int, bound):
+    if bound is None:
+        write_int(b, tag, _FB_UNBOUNDED_PRECEDING)
+    elif isinstance(bound, str):
+        assert bound == "U", bound
+        write_int(b, tag, _FB_UNBOUNDED_FOLLOWING)
+    elif isinstance(bound, float):
+        write_int(b, tag, _FB_OFFSET_DOUBLE)
+        write_double(b, tag + 2, bound)
+    else:
+        write_int(b, tag, _FB_OFFSET_INT)
+        write_int(b, tag + 1, int(bound))
+
+
+def _dec_frame_bound(m, tag: int, default):
+    kind = m.get(tag, [0])[-1]
+    if kind == 0:
+        return default
+    if kind == _FB_UNBOUNDED_PRECEDING:
+        return None
+    if kind == _FB_UNBOUNDED_FOLLOWING:
+        return "U"
+    if kind == _FB_OFFSET_INT:
+        return m.get(tag + 1, [0])[-1]
+    if kind == _FB_OFFSET_DOUBLE:
+        return m.get(tag + 2, [0.0])[-1]
+    raise ValueError(f"unknown FrameBoundKind {kind}")
 
 
 # ----------------------------------------------------------- task defs

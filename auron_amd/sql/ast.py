@@ -62,13 +62,24 @@ class FuncCall(ANode):
     over: Optional["WindowSpec"] = None
 
 
+@dataclass(frozen=True)
+class FrameOffset:
+    """RANGE frame value offset as written: `<text> PRECEDING|FOLLOWING`,
+    or `INTERVAL <text> <unit>`. The planner converts it to the ORDER BY
+    key's domain."""
+    sign: int  # -1 preceding, +1 following
+    text: str  # numeric literal text
+    unit: Optional[str] = None  # "day" for INTERVAL offsets
+
+
 @dataclass
 class WindowSpec(ANode):
     partition_by: List[ANode] = field(default_factory=list)
     order_by: List["OrderItem"] = field(default_factory=list)
     frame: Optional[str] = None  # "rows" | "range"
     # bounds: None = unbounded preceding, "U" = unbounded following,
-    # int = signed row offset (defaults = the SQL default frame)
+    # int = signed row offset (0 = current row), FrameOffset = RANGE value
+    # offset (defaults = the SQL default frame)
     frame_lo: object = None
     frame_hi: object = 0
 

@@ -2,14 +2,16 @@
 the TPC-DS suite the reference ships (dev/auron-it tpcds-queries/q*.sql):
 SELECT/DISTINCT, comma + ANSI joins (left/right/full outer), WHERE,
 GROUP BY [ROLLUP|CUBE]/GROUPING SETS, HAVING, window functions with
-PARTITION BY / ORDER BY / ROWS|RANGE frames (explicit ROWS bounds), WITH
-CTEs, UNION [ALL] / INTERSECT [ALL] / EXCEPT [ALL], scalar/IN/EXISTS
-subqueries, CASE, CAST, BETWEEN, LIKE, IN lists, INTERVAL arithmetic,
+PARTITION BY / ORDER BY / ROWS|RANGE frames (explicit ROWS row offsets;
+RANGE value offsets as integer/decimal literals or INTERVAL n DAY; a frame
+whose start lies after its end is rejected), WITH CTEs, UNION [ALL] /
+INTERSECT [ALL] / EXCEPT [ALL], scalar/IN/EXISTS subqueries, CASE, CAST, BETWEEN, LIKE, IN lists, INTERVAL arithmetic,
 ordinal ORDER BY references, NULLS FIRST/LAST, DATE/TIMESTAMP literals.
 """
 from __future__ import annotations
 
 import re
+from decimal import Decimal
 from typing import List, Optional, Tuple
 
 from . import ast as A
@@ -528,10 +530,14 @@ class Parser:
             spec.order_by = self._order_by()
         if self.at_kw("rows", "range"):
             spec.frame = self.advance().text
+            is_range = spec.frame == "range"
 
             def bound():
                 # -> None (unbounded preceding), "U" (unbounded following),
-                #    or signed row offset (preceding<0, current=0, following>0)
+                #    0 (current row), a signed row offset for ROWS
+                #    (preceding<0, following>0), or an A.FrameOffset for a
+                #    RANGE value offset (the planner converts it to the
+                #    ORDER BY key's domain)
                 if self.accept_kw("unbounded"):
                     if self.accept_kw("preceding"):
                         return None
@@ -540,21 +546,41 @@ class Parser:
                 if self.accept_kw("current"):
                     self.expect_kw("row")
                     return 0
-                if self.cur.kind != "num":
+                unit = None
+                if is_range and self.accept_kw("interval"):
+                    iv = self._interval()
+                    text, unit = str(iv.n), iv.unit
+                elif self.cur.kind == "num":
+                    text = self.advance().text
+                    if not is_range and not text.isdigit():
+                        self.fail("ROWS frame offsets must be integers")
+                else:
                     self.fail("expected frame bound")
-                k = int(self.advance().text)
                 if self.accept_kw("preceding"):
-                    return -k
-                self.expect_kw("following")
-                return k
+                    sign = -1
+                else:
+                    self.expect_kw("following")
+                    sign = 1
+                if is_range:
+                    return A.FrameOffset(sign, text, unit)
+                return sign * int(text)
+
+            def position(bv):
+                if bv is None:
+                    return (-1, 0)
+                if bv == "U":
+                    return (1, 0)
+                if isinstance(bv, A.FrameOffset):
+                    return (0, bv.sign * Decimal(bv.text))
+                return (0, Decimal(bv))
 
             self.expect_kw("between")
             spec.frame_lo = bound()
             self.expect_kw("and")
             spec.frame_hi = bound()
-            if spec.frame == "range" and not (
-                    spec.frame_lo is None and spec.frame_hi == 0):
-                self.fail("RANGE frames support only the default bounds")
+            if (spec.frame_lo == "U" or spec.frame_hi is None
+                    or position(spec.frame_lo) > position(spec.frame_hi)):
+                self.fail("window frame start lies after its end")
         self.expect_op(")")
         return spec
 

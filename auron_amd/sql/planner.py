@@ -1231,11 +1231,15 @@ class Planner:
             part = [self.to_expr(p, scope, ctx) for p in spec.partition_by]
             order = [(self.to_expr(oi.expr, scope, ctx), oi.ascending)
                      for oi in spec.order_by]
+            frame_lo = getattr(spec, "frame_lo", None)
+            frame_hi = getattr(spec, "frame_hi", 0)
+            if (spec.frame or "range") == "range":
+                frame_lo = self._range_frame_offset(frame_lo, order)
+                frame_hi = self._range_frame_offset(frame_hi, order)
             key = (tuple(expr_key(p) for p in part),
                    tuple((expr_key(e), a) for e, a in order),
                    spec.frame or "range",
-                   getattr(spec, "frame_lo", None),
-                   getattr(spec, "frame_hi", 0))
+                   frame_lo, frame_hi)
             groups.setdefault(key, []).append((fc, name, part, order))
         node = rel.node
         cols = list(rel.cols)
@@ -1253,6 +1257,60 @@ class Planner:
                            key[3], key[4])
         out = Rel(node, cols, rel.est, rel.base_dim_only)
         return out, Scope([out], scope.parent)
+
+    def _range_frame_offset(self, bound, order):
+        """RANGE frame bound -> plan value. A value offset is converted to
+        the domain of the single ORDER BY key: int for the int family
+        (same int), date32 (days), timestamp (microseconds) and decimal64
+        (unscaled), float for float keys."""
+        if not isinstance(bound, A.FrameOffset):
+            return bound  # unbounded / current row
+        written = (f"INTERVAL {bound.text} {bound.unit.upper()}"
+                   if bound.unit else bound.text)
+        written += " PRECEDING" if bound.sign < 0 else " FOLLOWING"
+        if len(order) != 1:
+            raise SqlError(
+                f"RANGE frame bound {written} needs exactly one ORDER BY "
+                f"key, got {len(order)}")
+        dt = infer_dtype(order[0][0], self.alloc.types)
+        if dt is None:
+            raise SqlError(
+                f"RANGE frame bound {written}: the ORDER BY key has no "
+                "known type")
+
+        def bad(why):
+            return SqlError(f"RANGE frame bound {written} does not fit a "
+                            f"{dt.name} ORDER BY key: {why}")
+
+        def signed(v: int) -> int:
+            if v > (1 << 63) - 1:
+                raise bad("the offset exceeds the int64 range")
+            return bound.sign * v
+
+        if bound.unit is not None:
+            n = int(bound.text)
+            if dt.code == dtypes.DATE32:
+                return signed(n)
+            if dt.code == dtypes.TIMESTAMP:
+                return signed(n * 86_400_000_000)
+            raise bad("an INTERVAL offset needs a date or timestamp key")
+        integral = bound.text.isdigit()
+        if dt.is_integer or dt.code == dtypes.DATE32:
+            if not integral:
+                raise bad("the offset must be an integer")
+            return signed(int(bound.text))
+        if dt.code == dtypes.TIMESTAMP:
+            raise bad("use INTERVAL n DAY")
+        if dt.code == dtypes.DECIMAL64:
+            whole, _, frac = bound.text.partition(".")
+            if len(frac.rstrip("0")) > dt.scale:
+                raise bad(f"more than {dt.scale} fractional digits")
+            frac = frac[:dt.scale].ljust(dt.scale, "0")
+            return signed(int((whole or "0") + frac))
+        if dt.is_float:
+            return bound.sign * float(bound.text)
+        raise bad("RANGE value offsets need an integer, date, timestamp, "
+                  "decimal64 or float key")
 
     def _window_func(self, fc: A.FuncCall, scope, ctx) -> WindowFunc:
         name = fc.name
