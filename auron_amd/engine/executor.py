@@ -2256,8 +2256,21 @@ class Executor:
                         names.append(al.name)
                         cols.append(out)
                         continue
-                    # running frames over decimal128: float64 accumulator
-                    # (precision-limited; exact running 128-bit: future)
+                    if (val.dtype.code == dtypes.DECIMAL128
+                            and wf.fn != "count"):
+                        # every other decimal128 frame: exact 128-bit
+                        # prefix / pyramid over the per-row frame (a, b)
+                        out = self._frame_aggregate_i128(
+                            wf.fn, val, *self._window_frame_bounds(
+                                node, sb, seg, seg_start, value_frame))
+                        self.ctx.metrics["window.frame_i128_rows"] = \
+                            self.ctx.metrics.get(
+                                "window.frame_i128_rows", 0) + n
+                        names.append(al.name)
+                        cols.append(out)
+                        continue
+                    # decimal64 sums wide enough to need 128 bits (and
+                    # count over decimal128): float64 accumulator
                     from ..exprs import _cast_col
 
                     val = _cast_col(val, dtypes.float64)
@@ -2485,6 +2498,99 @@ class Executor:
             b = last
         return a, b, a > b
 
+    def _window_frame_bounds(self, node, sb, seg, seg_start, value_frame):
+        """The Window node's frame as per-row inclusive (a, b, empty) over
+        the sorted rows, whatever its kind: an explicit RANGE frame
+        (`value_frame`, already resolved), bounded ROWS, the default running
+        frame (ROWS: up to the current row, RANGE: up to its last peer), or
+        the whole partition without ORDER BY."""
+        if value_frame is not None:
+            return value_frame
+        n = seg.numel()
+        device = seg.device
+        if n == 0:
+            z = torch.zeros(0, dtype=torch.int64, device=device)
+            return z, z, z > z
+        if node.frame == "rows" and not (node.frame_lo is None
+                                         and node.frame_hi == 0):
+            return self._rows_frame_bounds(
+                *self._partition_edges(seg, seg_start), node.frame_lo,
+                node.frame_hi)
+        a, b = self._partition_edges(seg, seg_start)
+        if node.order_by:
+            if node.frame == "range":
+                b = self._peer_end(node, sb, seg_start, n, device)
+            else:
+                b = torch.arange(n, dtype=torch.int64, device=device)
+        return a, b, a > b
+
+    @staticmethod
+    def _partition_edges(seg, seg_start):
+        """Per row: index of its partition's first and last row."""
+        n = seg.numel()
+        counts = torch.bincount(seg, minlength=int(seg.max().item()) + 1 if n else 1)
+        first = seg_start[seg]
+        return first, first + counts[seg] - 1
+
+    @staticmethod
+    def _rows_frame_bounds(first, last, lo, hi):
+        """ROWS BETWEEN lo AND hi (row offsets; None / "U" unbounded) ->
+        (a, b, empty), clamped to the row's partition [first, last]."""
+        i = torch.arange(first.numel(), dtype=torch.int64,
+                         device=first.device)
+        a = first if lo is None else torch.maximum(i + int(lo), first)
+        b = last if hi == "U" else torch.minimum(i + int(hi), last)
+        return a, b, a > b
+
+    @staticmethod
+    def _prefix_range(P, a, b, empty):
+        """P[b] - (a > 0 ? P[a-1] : 0) of an inclusive prefix array, zero
+        for an empty frame."""
+        hi_v = P[b.clamp(min=0)]
+        lo_i = a - 1
+        lo_v = torch.where(lo_i >= 0, P[lo_i.clamp(min=0)],
+                           torch.zeros((), dtype=P.dtype, device=P.device))
+        out = hi_v - lo_v
+        return torch.where(empty, torch.zeros_like(out), out)
+
+    def _frame_aggregate_i128(self, fn: str, val: Column, a: torch.Tensor,
+                              b: torch.Tensor, empty: torch.Tensor) -> Column:
+        """sum/avg/min/max of a DECIMAL128 column over per-row inclusive
+        frames [a, b], exact: sums are differences of one unsegmented
+        128-bit prefix sum (wrapped prefixes cancel), min/max come from the
+        128-bit frame primitive. Nulls are skipped; a frame with no valid
+        value gives NULL. sum/min/max keep the argument's type, avg is
+        float64."""
+        assert val.dtype.code == dtypes.DECIMAL128, val.dtype
+        device = a.device
+        valid = val.validity
+        if valid is None:
+            cnt = torch.where(empty, torch.zeros_like(a), b - a + 1)
+        else:
+            cnt = self._prefix_range(torch.cumsum(valid.to(torch.int64), 0),
+                                     a, b, empty)
+        validity = compact_validity(cnt > 0)
+        if fn in ("sum", "avg"):
+            s = ops.window_frame_sum_i128(
+                ops.prefix_sum_i128(val.data, valid), a, b)
+            if fn == "sum":
+                return Column(val.dtype, s, validity)
+            from ..exprs import dec128_to_float64
+
+            data = dec128_to_float64(s, val.dtype.scale) \
+                / cnt.clamp(min=1).to(torch.float64)
+            return Column(dtypes.float64, data, validity)
+        assert fn in ("min", "max"), fn
+        x = val.data
+        if valid is not None:
+            ident = torch.tensor(
+                ops._I128_MAX if fn == "min" else ops._I128_MIN,
+                dtype=torch.int64, device=device)
+            x = torch.where(valid.unsqueeze(1), x, ident)
+        # an empty frame (a > b) yields the identity; cnt == 0 makes it NULL
+        m = ops.window_frame_minmax_i128(x, a, b, fn)
+        return Column(val.dtype, m, validity)
+
     def _frame_aggregate(self, fn: str, val: Column, a: torch.Tensor,
                          b: torch.Tensor, empty: torch.Tensor) -> Column:
         """sum/avg/count/min/max over per-row inclusive frames [a, b]
@@ -2498,12 +2604,7 @@ class Executor:
         C = torch.cumsum(valid.to(torch.int64), 0)
 
         def rng(P):
-            hi_v = P[b.clamp(min=0)]
-            lo_i = a - 1
-            lo_v = torch.where(lo_i >= 0, P[lo_i.clamp(min=0)],
-                               torch.zeros((), dtype=P.dtype, device=device))
-            out = hi_v - lo_v
-            return torch.where(empty, torch.zeros_like(out), out)
+            return self._prefix_range(P, a, b, empty)
 
         cnt = rng(C)
         if fn == "count":
@@ -2548,13 +2649,9 @@ class Executor:
         frame min/max primitive (unbounded side or span >= 1024)."""
         device = seg.device
         n = seg.numel()
-        counts = torch.bincount(seg, minlength=int(seg.max().item()) + 1 if n else 1)
-        first = seg_start[seg]
-        last = first + counts[seg] - 1
+        first, last = self._partition_edges(seg, seg_start)
+        a, b, empty = self._rows_frame_bounds(first, last, lo, hi)
         i = torch.arange(n, dtype=torch.int64, device=device)
-        a = first if lo is None else torch.maximum(i + int(lo), first)
-        b = last if hi == "U" else torch.minimum(i + int(hi), last)
-        empty = a > b
         valid = val.validity if val.validity is not None else \
             torch.ones(n, dtype=torch.bool, device=device)
         if fn in ("sum", "avg", "count"):

@@ -96,8 +96,16 @@ def _try_load():
                                                ctypes.c_int, c, c]
     lib.au_window_pyramid_size.argtypes = [i64]
     lib.au_window_pyramid_size.restype = i64
+    lib.au_i128_scan_tile.argtypes = []
+    lib.au_i128_scan_tile.restype = i64
+    lib.au_prefix_sum_i128.argtypes = [c, c, i64, c, c, c]
+    lib.au_window_frame_sum_i128.argtypes = [c, i64, c, c, i64, c, c]
+    lib.au_window_frame_minmax_i128.argtypes = [c, i64, c, i64, c, c, i64,
+                                                ctypes.c_int, c, c]
     for f in ("au_window_range_bounds_i64", "au_window_range_bounds_f64",
-              "au_window_frame_minmax_i64", "au_window_frame_minmax_f64"):
+              "au_window_frame_minmax_i64", "au_window_frame_minmax_f64",
+              "au_prefix_sum_i128", "au_window_frame_sum_i128",
+              "au_window_frame_minmax_i128"):
         getattr(lib, f).restype = ctypes.c_int
     for f in ("au_murmur3", "au_group_ids", "au_join_build", "au_join_count",
               "au_join_fill", "au_pmod", "au_part_hist", "au_part_scatter"):

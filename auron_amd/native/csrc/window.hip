@@ -1,6 +1,6 @@
 // Auron-AMD native engine — window frame kernels, gfx950 (MI355X, CDNA4) only.
 //
-// Two primitives behind "aggregate over an arbitrary per-row frame [a, b]":
+// The primitives behind "aggregate over an arbitrary per-row frame [a, b]":
 //
 //   au_window_range_bounds_{i64,f64}
 //     RANGE frames with value offsets. One row per thread, grid-stride.
@@ -23,6 +23,15 @@
 //     back in one caller-provided buffer (au_window_pyramid_size entries).
 //     One wave64 reduces one tile with __shfl_xor. Floating NaN propagates
 //     (torch.minimum / torch.maximum semantics).
+//
+//   au_prefix_sum_i128 / au_window_frame_sum_i128 / au_window_frame_minmax_i128
+//     The same frame aggregates over 128-bit integers (decimal128 backing:
+//     [lo bit pattern, hi signed] int64 pairs, row-major [n,2]). Sums are a
+//     difference of two entries of one unsegmented inclusive prefix sum
+//     modulo 2^128 — wrapped prefixes cancel in the difference — built in
+//     three launches (tile totals, one-block scan of the totals, per-tile
+//     rescan) so no workgroup ever waits on another. Min/max instantiate
+//     the pyramid above for the limb pair.
 //
 // C ABI only — loaded via ctypes from auron_amd/native/__init__.py.
 // All pointers are device pointers owned by torch; `stream` is the torch
@@ -323,4 +332,267 @@ AU_EXPORT int au_window_frame_minmax_f64(const double* x, int64_t n,
                                          void* stream) {
   return wn_frame_minmax<double>(x, n, pyr, pyr_len, a, b, rows, is_max, out,
                                  stream);
+}
+
+// ===================================================== 128-bit frame kernels
+// One decimal128 value. 16-byte aligned so a load/store is one dwordx4.
+struct alignas(16) WnI128 {
+  uint64_t lo;  // low 64 bits, bit pattern
+  int64_t hi;   // high 64 bits, signed
+};
+
+__device__ __forceinline__ WnI128 wn_add128(WnI128 x, WnI128 y) {
+  WnI128 r;
+  r.lo = x.lo + y.lo;
+  r.hi = (int64_t)((uint64_t)x.hi + (uint64_t)y.hi + (r.lo < x.lo ? 1u : 0u));
+  return r;
+}
+__device__ __forceinline__ WnI128 wn_sub128(WnI128 x, WnI128 y) {
+  WnI128 r;
+  r.lo = x.lo - y.lo;
+  r.hi = (int64_t)((uint64_t)x.hi - (uint64_t)y.hi - (x.lo < y.lo ? 1u : 0u));
+  return r;
+}
+__device__ __forceinline__ WnI128 wn_zero128() {
+  WnI128 r;
+  r.lo = 0;
+  r.hi = 0;
+  return r;
+}
+__device__ __forceinline__ WnI128 wn_shfl_up128(WnI128 v, int d) {
+  WnI128 r;
+  r.lo = (uint64_t)__shfl_up((unsigned long long)v.lo, d, WN_TILE);
+  r.hi = (int64_t)__shfl_up((long long)v.hi, d, WN_TILE);
+  return r;
+}
+
+// ------------------------------------------------------------- prefix sum
+#define WN_SCAN_BLOCK 256
+#define WN_SCAN_ITEMS 4  // consecutive elements per thread
+#define WN_SCAN_TILE (WN_SCAN_BLOCK * WN_SCAN_ITEMS)
+#define WN_SCAN_WAVES (WN_SCAN_BLOCK / WN_TILE)
+
+AU_EXPORT int64_t au_i128_scan_tile() { return WN_SCAN_TILE; }
+
+// Inclusive scan of one value per thread over a 256-thread block: wave64
+// scan with __shfl_up (every lane reaches every shuffle; only the add is
+// predicated), wave totals through LDS. Returns the inclusive prefix and
+// the block total. Every thread of the block must call it; `wtot` may be
+// reused after the call (barrier at both ends).
+__device__ __forceinline__ WnI128 wn_block_scan128(WnI128 v, WnI128* wtot,
+                                                   WnI128* block_total) {
+  const int lane = threadIdx.x & (WN_TILE - 1);
+  const int wave = threadIdx.x / WN_TILE;
+#pragma unroll
+  for (int d = 1; d < WN_TILE; d <<= 1) {
+    const WnI128 up = wn_shfl_up128(v, d);
+    const WnI128 s = wn_add128(v, up);
+    if (lane >= d) v = s;
+  }
+  __syncthreads();  // earlier readers of wtot are done
+  if (lane == WN_TILE - 1) wtot[wave] = v;
+  __syncthreads();
+  WnI128 off = wn_zero128(), tot = wn_zero128();
+#pragma unroll
+  for (int w = 0; w < WN_SCAN_WAVES; w++) {
+    const WnI128 t = wtot[w];
+    if (w < wave) off = wn_add128(off, t);
+    tot = wn_add128(tot, t);
+  }
+  *block_total = tot;
+  return wn_add128(v, off);
+}
+
+// Loads the thread's WN_SCAN_ITEMS consecutive elements of tile `t`; rows
+// past n or with valid[i] == 0 read as zero.
+__device__ __forceinline__ void wn_scan_load(const WnI128* __restrict__ x,
+                                             const uint8_t* __restrict__ valid,
+                                             int64_t n, int64_t t,
+                                             WnI128 v[WN_SCAN_ITEMS]) {
+  const int64_t base = t * WN_SCAN_TILE + (int64_t)threadIdx.x * WN_SCAN_ITEMS;
+#pragma unroll
+  for (int k = 0; k < WN_SCAN_ITEMS; k++) {
+    const int64_t i = base + k;
+    v[k] = wn_zero128();
+    if (i < n && (valid == nullptr || valid[i] != 0)) v[k] = x[i];
+  }
+}
+
+// pass 1: totals[t] = sum of tile t
+__global__ void __launch_bounds__(WN_SCAN_BLOCK)
+k_i128_tile_totals(const WnI128* __restrict__ x,
+                   const uint8_t* __restrict__ valid, int64_t n,
+                   int64_t tiles, WnI128* __restrict__ totals) {
+  __shared__ WnI128 wtot[WN_SCAN_WAVES];
+  const int lane = threadIdx.x & (WN_TILE - 1);
+  const int wave = threadIdx.x / WN_TILE;
+  // block-uniform loop: all 256 threads reach every shuffle and barrier
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    WnI128 v[WN_SCAN_ITEMS];
+    wn_scan_load(x, valid, n, t, v);
+    WnI128 s = v[0];
+#pragma unroll
+    for (int k = 1; k < WN_SCAN_ITEMS; k++) s = wn_add128(s, v[k]);
+#pragma unroll
+    for (int d = WN_TILE / 2; d >= 1; d >>= 1) {
+      WnI128 o;
+      o.lo = (uint64_t)__shfl_xor((unsigned long long)s.lo, d, WN_TILE);
+      o.hi = (int64_t)__shfl_xor((long long)s.hi, d, WN_TILE);
+      s = wn_add128(s, o);
+    }
+    __syncthreads();  // the previous tile's reader is done
+    if (lane == 0) wtot[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      WnI128 tot = wtot[0];
+#pragma unroll
+      for (int w = 1; w < WN_SCAN_WAVES; w++) tot = wn_add128(tot, wtot[w]);
+      totals[t] = tot;
+    }
+  }
+}
+
+// pass 2 (one block): totals[t] <- sum of totals[0 .. t-1], in place,
+// 256 tiles per round with a running carry
+__global__ void __launch_bounds__(WN_SCAN_BLOCK)
+k_i128_scan_totals(WnI128* __restrict__ totals, int64_t tiles) {
+  __shared__ WnI128 wtot[WN_SCAN_WAVES];
+  WnI128 carry = wn_zero128();
+  for (int64_t c = 0; c < tiles; c += WN_SCAN_BLOCK) {  // block-uniform
+    const int64_t t = c + threadIdx.x;
+    const WnI128 own = t < tiles ? totals[t] : wn_zero128();
+    WnI128 round_total;
+    const WnI128 incl = wn_block_scan128(own, wtot, &round_total);
+    if (t < tiles) totals[t] = wn_add128(carry, wn_sub128(incl, own));
+    carry = wn_add128(carry, round_total);
+  }
+}
+
+// pass 3: out[i] = offsets[tile(i)] + inclusive prefix inside the tile
+__global__ void __launch_bounds__(WN_SCAN_BLOCK)
+k_i128_tile_rescan(const WnI128* __restrict__ x,
+                   const uint8_t* __restrict__ valid, int64_t n,
+                   int64_t tiles, const WnI128* __restrict__ offsets,
+                   WnI128* __restrict__ out) {
+  __shared__ WnI128 wtot[WN_SCAN_WAVES];
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {  // block-uniform
+    WnI128 v[WN_SCAN_ITEMS];
+    wn_scan_load(x, valid, n, t, v);
+#pragma unroll
+    for (int k = 1; k < WN_SCAN_ITEMS; k++) v[k] = wn_add128(v[k], v[k - 1]);
+    const WnI128 own = v[WN_SCAN_ITEMS - 1];
+    WnI128 tile_total;
+    const WnI128 incl = wn_block_scan128(own, wtot, &tile_total);
+    const WnI128 excl = wn_add128(offsets[t], wn_sub128(incl, own));
+    const int64_t base =
+        t * WN_SCAN_TILE + (int64_t)threadIdx.x * WN_SCAN_ITEMS;
+#pragma unroll
+    for (int k = 0; k < WN_SCAN_ITEMS; k++)
+      if (base + k < n) out[base + k] = wn_add128(excl, v[k]);
+  }
+}
+
+static inline int wn_tile_grid(int64_t tiles) {
+  return (int)(tiles > 2048 ? 2048 : tiles);
+}
+
+// out[i] = (x[0] + ... + x[i]) mod 2^128 over [n,2] limb pairs; a row with
+// valid[i] == 0 adds zero (valid == NULL: every row counts). tile_scratch
+// holds ceil(n / au_i128_scan_tile()) limb pairs. out may not alias x.
+AU_EXPORT int au_prefix_sum_i128(const int64_t* x, const uint8_t* valid,
+                                 int64_t n, int64_t* out,
+                                 int64_t* tile_scratch, void* stream) {
+  if (n <= 0) return 0;
+  if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)tile_scratch) & 15)
+    return (int)hipErrorInvalidValue;
+  const int64_t tiles = (n + WN_SCAN_TILE - 1) / WN_SCAN_TILE;
+  const WnI128* xv = (const WnI128*)x;
+  WnI128* tot = (WnI128*)tile_scratch;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_i128_tile_totals, dim3(wn_tile_grid(tiles)),
+                     dim3(WN_SCAN_BLOCK), 0, s, xv, valid, n, tiles, tot);
+  int rc = (int)hipGetLastError();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_i128_scan_totals, dim3(1), dim3(WN_SCAN_BLOCK), 0, s,
+                     tot, tiles);
+  rc = (int)hipGetLastError();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_i128_tile_rescan, dim3(wn_tile_grid(tiles)),
+                     dim3(WN_SCAN_BLOCK), 0, s, xv, valid, n, tiles,
+                     (const WnI128*)tot, (WnI128*)out);
+  return (int)hipGetLastError();
+}
+
+// --------------------------------------------------------------- frame sum
+__global__ void k_window_frame_sum_i128(const WnI128* __restrict__ P,
+                                        int64_t n,
+                                        const int64_t* __restrict__ a,
+                                        const int64_t* __restrict__ b,
+                                        int64_t rows,
+                                        WnI128* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t lo = a[i], hi = b[i];
+    // never index outside P, whatever the caller passed
+    if (lo < 0) lo = 0;
+    if (hi > n - 1) hi = n - 1;
+    WnI128 r = wn_zero128();
+    if (lo <= hi) {
+      r = P[hi];
+      if (lo > 0) r = wn_sub128(r, P[lo - 1]);
+    }
+    out[i] = r;
+  }
+}
+
+// out[i] = P[b[i]] - (a[i] > 0 ? P[a[i]-1] : 0) mod 2^128 for i < rows, zero
+// when a[i] > b[i]; P is the [n,2] inclusive prefix sum. Frames are clamped
+// to [0, n-1] like au_window_frame_minmax.
+AU_EXPORT int au_window_frame_sum_i128(const int64_t* P, int64_t n,
+                                       const int64_t* a, const int64_t* b,
+                                       int64_t rows, int64_t* out,
+                                       void* stream) {
+  if (rows <= 0) return 0;
+  if (((uintptr_t)P | (uintptr_t)out) & 15) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_window_frame_sum_i128, dim3(wn_grid(rows, 256)),
+                     dim3(256), 0, (hipStream_t)stream, (const WnI128*)P, n,
+                     a, b, rows, (WnI128*)out);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------ frame min/max
+// Order: signed hi first, then unsigned lo.
+template <bool IS_MAX>
+struct WnOp<WnI128, IS_MAX> {
+  static __host__ __device__ __forceinline__ WnI128 identity() {
+    WnI128 r;  // min: 2^127 - 1, max: -2^127
+    r.lo = IS_MAX ? 0 : ~(uint64_t)0;
+    r.hi = IS_MAX ? INT64_MIN : INT64_MAX;
+    return r;
+  }
+  static __device__ __forceinline__ bool less(WnI128 x, WnI128 y) {
+    return x.hi < y.hi || (x.hi == y.hi && x.lo < y.lo);
+  }
+  static __device__ __forceinline__ WnI128 combine(WnI128 x, WnI128 y) {
+    return (IS_MAX ? less(x, y) : less(y, x)) ? y : x;
+  }
+  static __device__ __forceinline__ WnI128 shfl_xor(WnI128 v, int m) {
+    WnI128 r;
+    r.lo = (uint64_t)__shfl_xor((unsigned long long)v.lo, m, WN_TILE);
+    r.hi = (int64_t)__shfl_xor((long long)v.hi, m, WN_TILE);
+    return r;
+  }
+};
+
+// As au_window_frame_minmax_i64 over [n,2] limb pairs; `pyr` is scratch of
+// at least au_window_pyramid_size(n) pairs, out is [rows,2].
+AU_EXPORT int au_window_frame_minmax_i128(const int64_t* x, int64_t n,
+                                          int64_t* pyr, int64_t pyr_len,
+                                          const int64_t* a, const int64_t* b,
+                                          int64_t rows, int is_max,
+                                          int64_t* out, void* stream) {
+  if (((uintptr_t)x | (uintptr_t)pyr | (uintptr_t)out) & 15)
+    return (int)hipErrorInvalidValue;
+  return wn_frame_minmax<WnI128>((const WnI128*)x, n, (WnI128*)pyr, pyr_len,
+                                 a, b, rows, is_max, (WnI128*)out, stream);
 }

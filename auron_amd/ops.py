@@ -705,6 +705,207 @@ def window_frame_minmax(x: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
     return out
 
 
+# ------------------------------------------------- 128-bit frame aggregates
+# A 128-bit value is two int64 limbs [lo bit pattern, hi signed], row-major
+# [n,2] — the layout Column uses for DECIMAL128.
+_I128_MAX = (-1, _MAX64)  # 2^127 - 1: identity of min
+_I128_MIN = (0, _MIN64)   # -2^127:    identity of max
+
+
+def _i128_args(x, valid=None):
+    assert x.dtype == torch.int64 and x.dim() == 2 and x.shape[1] == 2, \
+        f"expected int64 [n,2] limbs, got {x.dtype} {tuple(x.shape)}"
+    assert x.shape[0] < (1 << 31), "batch too large for split accumulation"
+    if valid is not None:
+        assert valid.dtype == torch.bool and valid.numel() == x.shape[0]
+
+
+def _i128_frame_args(a, b):
+    assert a.dtype == torch.int64 and b.dtype == torch.int64
+    assert a.numel() == b.numel()
+
+
+def _i128_aligned(t: torch.Tensor) -> torch.Tensor:
+    """Contiguous and 16-byte aligned, as the kernels' 16-byte loads need."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _ult(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """Unsigned x < y over int64 bit patterns: flip the sign bit, then
+    compare signed."""
+    return (x ^ _MIN64) < (y ^ _MIN64)
+
+
+def prefix_sum_i128_ref(x: torch.Tensor,
+                        valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Oracle for prefix_sum_i128 (pure torch): four 32-bit digits (top one
+    signed), each cumsum-ed in int64 and recomposed with carry propagation,
+    as in the group-by decimal128 sum. Below 2^31 rows no digit sum can
+    leave int64."""
+    _i128_args(x, valid)
+    lo, hi = x[:, 0], x[:, 1]
+    if valid is not None:
+        z = torch.zeros((), dtype=torch.int64, device=x.device)
+        lo, hi = torch.where(valid, lo, z), torch.where(valid, hi, z)
+    m = 0xFFFFFFFF
+    s0, s1, s2, s3 = (torch.cumsum(d, 0) for d in
+                      (lo & m, (lo >> 32) & m, hi & m, hi >> 32))
+    t1 = s1 + (s0 >> 32)
+    t2 = s2 + (t1 >> 32)
+    t3 = s3 + (t2 >> 32)
+    return torch.stack([((t1 & m) << 32) | (s0 & m),
+                        (t3 << 32) | (t2 & m)], dim=1)
+
+
+def prefix_sum_i128(x: torch.Tensor,
+                    valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Inclusive prefix sum modulo 2^128 over int64 [n,2] limb pairs; a row
+    whose `valid` is False adds zero. The scan is not segmented: a frame sum
+    is a difference of two prefixes (window_frame_sum_i128), in which
+    wrapped prefixes cancel."""
+    _i128_args(x, valid)
+    device = x.device
+    if not _use_native(device):
+        return prefix_sum_i128_ref(x, valid)
+    lib = native.lib()
+    n = x.shape[0]
+    out = torch.empty((n, 2), dtype=torch.int64, device=device)
+    if n == 0:
+        return out
+    x = _i128_aligned(x)
+    vptr = None
+    if valid is not None:
+        valid = valid.contiguous()
+        vptr = valid.data_ptr()
+    tile = int(lib.au_i128_scan_tile())
+    scratch = torch.empty(((n + tile - 1) // tile, 2), dtype=torch.int64,
+                          device=device)
+    rc = lib.au_prefix_sum_i128(x.data_ptr(), vptr, n, out.data_ptr(),
+                                scratch.data_ptr(), native.stream_ptr(device))
+    native.check(rc, "au_prefix_sum_i128")
+    return out
+
+
+def window_frame_sum_i128_ref(P: torch.Tensor, a: torch.Tensor,
+                              b: torch.Tensor) -> torch.Tensor:
+    """Oracle for window_frame_sum_i128 (pure torch): limb subtraction, the
+    borrow from an unsigned compare of the low limbs."""
+    _i128_args(P)
+    _i128_frame_args(a, b)
+    n = P.shape[0]
+    rows = a.numel()
+    lo = a.clamp(min=0)
+    hi = b.clamp(max=n - 1)
+    empty = lo > hi
+    if n == 0 or rows == 0:
+        return torch.zeros((rows, 2), dtype=torch.int64, device=P.device)
+    top = P[hi.clamp(min=0)]
+    below = torch.where((lo > 0).unsqueeze(1), P[(lo - 1).clamp(0, n - 1)],
+                        torch.zeros((), dtype=torch.int64, device=P.device))
+    d_lo = top[:, 0] - below[:, 0]
+    borrow = _ult(top[:, 0], below[:, 0]).to(torch.int64)
+    d_hi = top[:, 1] - below[:, 1] - borrow
+    out = torch.stack([d_lo, d_hi], dim=1)
+    return torch.where(empty.unsqueeze(1), torch.zeros_like(out), out)
+
+
+def window_frame_sum_i128(P: torch.Tensor, a: torch.Tensor,
+                          b: torch.Tensor) -> torch.Tensor:
+    """Per-row sum over the inclusive frame [a[i], b[i]] from the inclusive
+    128-bit prefix sum P (prefix_sum_i128): P[b] - (a > 0 ? P[a-1] : 0)
+    modulo 2^128, zero for an empty frame (a > b). Exact whenever the frame
+    sum itself fits in 128 bits. Frames are clamped to [0, n-1]."""
+    _i128_args(P)
+    _i128_frame_args(a, b)
+    device = P.device
+    if not _use_native(device):
+        return window_frame_sum_i128_ref(P, a, b)
+    lib = native.lib()
+    rows = a.numel()
+    out = torch.empty((rows, 2), dtype=torch.int64, device=device)
+    if rows == 0:
+        return out
+    P, a, b = _i128_aligned(P), a.contiguous(), b.contiguous()
+    rc = lib.au_window_frame_sum_i128(P.data_ptr(), P.shape[0], a.data_ptr(),
+                                      b.data_ptr(), rows, out.data_ptr(),
+                                      native.stream_ptr(device))
+    native.check(rc, "au_window_frame_sum_i128")
+    return out
+
+
+def _i128_less(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """x < y over [m,2] limb pairs: signed hi first, then unsigned lo."""
+    return (x[:, 1] < y[:, 1]) | ((x[:, 1] == y[:, 1])
+                                  & _ult(x[:, 0], y[:, 0]))
+
+
+def window_frame_minmax_i128_ref(x: torch.Tensor, a: torch.Tensor,
+                                 b: torch.Tensor, op: str) -> torch.Tensor:
+    """Oracle for window_frame_minmax_i128 (pure torch): the doubling sparse
+    table of window_frame_minmax_ref with a 128-bit less-than."""
+    assert op in ("min", "max"), op
+    _i128_args(x)
+    _i128_frame_args(a, b)
+    n = x.shape[0]
+
+    def combine(p, q):
+        take_q = _i128_less(q, p) if op == "min" else _i128_less(p, q)
+        return torch.where(take_q.unsqueeze(1), q, p)
+
+    ident = torch.tensor(_I128_MAX if op == "min" else _I128_MIN,
+                         dtype=torch.int64, device=x.device)
+    out = ident.repeat(a.numel(), 1)
+    lo = a.clamp(min=0)
+    hi = b.clamp(max=n - 1)
+    ln = hi - lo + 1
+    if a.numel() == 0 or n == 0 or int(ln.max().item()) <= 0:
+        return out
+    level = x
+    k = 0
+    maxlen = int(ln.max().item())
+    while True:
+        w = 1 << k
+        sel = (ln >= w) & (ln < 2 * w)
+        if bool(sel.any()):
+            out[sel] = combine(level[lo[sel]], level[hi[sel] - w + 1])
+        if 2 * w > maxlen:
+            break
+        nxt = level.clone()
+        nxt[:n - w] = combine(level[:n - w], level[w:])
+        level = nxt
+        k += 1
+    return out
+
+
+def window_frame_minmax_i128(x: torch.Tensor, a: torch.Tensor,
+                             b: torch.Tensor, op: str) -> torch.Tensor:
+    """window_frame_minmax over int64 [n,2] limb pairs (signed 128-bit
+    order) -> [rows,2]. Nulls must already be replaced by the identity
+    (2^127-1 for min, -2^127 for max); an empty frame yields it."""
+    assert op in ("min", "max"), op
+    _i128_args(x)
+    _i128_frame_args(a, b)
+    device = x.device
+    if not _use_native(device):
+        return window_frame_minmax_i128_ref(x, a, b, op)
+    lib = native.lib()
+    n = x.shape[0]
+    rows = a.numel()
+    out = torch.empty((rows, 2), dtype=torch.int64, device=device)
+    if rows == 0:
+        return out
+    assert n > 0, "window_frame_minmax_i128: frames over an empty array"
+    x, a, b = _i128_aligned(x), a.contiguous(), b.contiguous()
+    pyr_len = int(lib.au_window_pyramid_size(n))  # levels above x
+    pyr = torch.empty((max(pyr_len, 1), 2), dtype=torch.int64, device=device)
+    rc = lib.au_window_frame_minmax_i128(
+        x.data_ptr(), n, pyr.data_ptr(), pyr_len, a.data_ptr(), b.data_ptr(),
+        rows, int(op == "max"), out.data_ptr(), native.stream_ptr(device))
+    native.check(rc, "au_window_frame_minmax_i128")
+    return out
+
+
 # ================================================================ partition
 def _normalize_hash_col(c: Column) -> Column:
     """Promote key columns to a canonical width before hashing: murmur3
