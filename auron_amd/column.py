@@ -286,6 +286,18 @@ class Column:
                 data = torch.from_numpy(np.frombuffer(buf, dtype=np.uint8, count=end - start, offset=start))
                 offsets = torch.from_numpy(off_np if start == 0 else off_np - start)
             col = Column(dt, data, validity, offsets)
+        elif dt.is_list:
+            import pyarrow.compute as pc
+
+            child = arr.flatten()  # slice-aware; null lists contribute nothing
+            if child.null_count:
+                raise TypeError("list columns with NULL elements are unsupported")
+            lens = pc.list_value_length(arr).fill_null(0).to_numpy(
+                zero_copy_only=False).astype(np.int64)
+            off_np = np.zeros(len(arr) + 1, dtype=np.int64)
+            np.cumsum(lens, out=off_np[1:])
+            data = Column.from_arrow(child).data.to(dt.torch_dtype)
+            col = Column(dt, data, validity, torch.from_numpy(off_np))
         elif dt.code == dtypes.DECIMAL64:
             d128 = arr.cast(pa.decimal128(dt.precision, dt.scale))
             d128 = d128.combine_chunks() if isinstance(d128, pa.ChunkedArray) else d128

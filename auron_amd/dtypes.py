@@ -171,6 +171,11 @@ def from_arrow(at) -> DataType:
         return decimal64(at.precision, at.scale)
     if pa.types.is_dictionary(at):
         return from_arrow(at.value_type)
+    if pa.types.is_list(at) or pa.types.is_large_list(at):
+        child = from_arrow(at.value_type)
+        if child.code in (LIST, STRING, DECIMAL128):
+            raise TypeError(f"unsupported arrow list element type {at}")
+        return list_of(child)
     raise TypeError(f"unsupported arrow type {at}")
 
 

@@ -71,6 +71,14 @@ def _try_load():
     lib.au_host_plainba_parse.restype = i64
     lib.au_host_delta_unpack.argtypes = [c, i64, i64, i64, ctypes.c_int, c]
     lib.au_host_delta_unpack.restype = i64
+    lib.au_host_delta_index.argtypes = [c, i64, i64, i64, i64, i64, i64, c, c,
+                                        i64]
+    lib.au_host_delta_index.restype = i64
+    lib.au_pq_delta_sums.argtypes = [c, i64, c, c, c]
+    lib.au_pq_delta_scan.argtypes = [c, i64, c]
+    lib.au_pq_delta_emit.argtypes = [c, i64, c, i64, c, c, c, ctypes.c_int, c]
+    for f in ("au_pq_delta_sums", "au_pq_delta_scan", "au_pq_delta_emit"):
+        getattr(lib, f).restype = ctypes.c_int
     lib.au_pq_rle_idx.argtypes = [c, ctypes.c_int, c, c, c, c]
     lib.au_pq_scatter.argtypes = [c, ctypes.c_int, c, c, c, c, ctypes.c_int, i64, c]
     lib.au_pq_copy_plain.argtypes = [c, ctypes.c_int, c, c, ctypes.c_int, i64, c]

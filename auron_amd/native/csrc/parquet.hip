@@ -9,6 +9,8 @@
 //                    precomputed validity prefix sum
 //  - k_pq_copy:      PLAIN values for required (no-null) chunks, segmented
 //                    vectorized copy
+//  - k_pq_delta_*:   DELTA_BINARY_PACKED values and DELTA_LENGTH_BYTE_ARRAY
+//                    lengths, one wave per miniblock (host-indexed headers)
 //
 // Page descriptor layout (int64 x 6, packed by parquet_native.py):
 //   [0]=def_off [1]=def_len [2]=values_off [3]=n_values [4]=row_start [5]=pad
@@ -477,10 +479,12 @@ AU_EXPORT int64_t au_host_plainba_parse(const uint8_t* buf, int64_t off,
 }
 
 // Host-side DELTA_BINARY_PACKED decode (parquet encoding 5) into PLAIN
-// little-endian values (esize 4 or 8). The format is inherently serial
-// (varint headers, running prefix value); decoded pages then ride the
-// same device PLAIN path as everything else. Returns values written,
-// -1 on corruption.
+// little-endian values (esize 4 or 8). Serial reference decoder: it is
+// the scan path only when spark.auron.scan.deltaNative.enable is off
+// (one "delta" host job per page, expanded bytes uploaded as PLAIN).
+// With the switch on, au_host_delta_index below walks just the headers
+// and the k_pq_delta_* kernels decode the values on the device.
+// Returns values written, -1 on corruption.
 static inline int64_t du_uvarint(const uint8_t* b, int64_t end, int64_t* pos,
                                  uint64_t* out) {
   uint64_t v = 0; int shift = 0;
@@ -489,6 +493,7 @@ static inline int64_t du_uvarint(const uint8_t* b, int64_t end, int64_t* pos,
     v |= (uint64_t)(x & 0x7F) << shift;
     if (!(x & 0x80)) { *out = v; return 0; }
     shift += 7;
+    if (shift > 63) return -1;
   }
   return -1;
 }
@@ -549,4 +554,272 @@ AU_EXPORT int64_t au_host_delta_unpack(const uint8_t* buf, int64_t off,
   }
   #undef EMIT
   return count;
+}
+
+// ------------------------------------------------- DELTA_BINARY_PACKED
+// Device decode of parquet encoding 5 (and of the length stream of
+// encoding 6, DELTA_LENGTH_BYTE_ARRAY). Only the header walk is serial:
+// one varint plus a few bit-width bytes per block. The host does that
+// walk once per file (au_host_delta_index) and emits descriptors; the
+// values are a bit-unpack plus a prefix sum and run here, one wave per
+// miniblock:
+//   k_pq_delta_sums   sums[m]  = sum of (min_delta + packed delta) of m
+//   k_pq_delta_scan   sums[m] <- exclusive scan over the whole chunk
+//   k_pq_delta_emit   value    = page first + (scan[m] - scan[page's
+//                     first miniblock]) + inclusive wave scan inside m
+// All arithmetic is unsigned 64-bit, i.e. exact under two's-complement
+// wrap; INT32 columns keep the low 32 bits. No delta array is written
+// to HBM: the emit kernel unpacks a second time instead.
+//
+// Page descriptor (int64 x 5):
+//   [0]=first value  [1]=total values in the stream header
+//   [2]=absolute byte offset of the stream's end
+//   [3]=compact output index of the first value
+//   [4]=index of the page's first miniblock descriptor
+// Miniblock descriptor (int64 x 4), only miniblocks that hold values:
+//   [0]=absolute byte offset of the bit data  [1]=min_delta
+//   [2]=compact output index of its first value
+//   [3]=bit width | values held << 8 | page index << 32
+struct DlPage {
+  int64_t first;
+  int64_t total;
+  int64_t end;
+  int64_t out_base;
+  int64_t mb_begin;
+};
+
+struct DlMini {
+  int64_t byte_off;
+  int64_t min_delta;
+  int64_t out_idx;
+  int64_t packed;
+};
+
+#define DL_MAX_BLOCK (1 << 24)  // values held must fit the 24-bit field
+
+// Walks one page's stream; writes pg[5] and up to `cap` miniblock
+// descriptors at `mb`. Returns the number of miniblocks, -1 on a corrupt
+// or unsupported stream. Trailing miniblocks of the last block that hold
+// no value are skipped without looking at their bit-width byte.
+AU_EXPORT int64_t au_host_delta_index(const uint8_t* buf, int64_t off,
+                                      int64_t len, int64_t n_rows,
+                                      int64_t out_base, int64_t page_id,
+                                      int64_t mb_begin, int64_t* pg,
+                                      int64_t* mb, int64_t cap) {
+  int64_t pos = off;
+  const int64_t end = off + len;
+  uint64_t block_size, nmini, total, ufirst;
+  if (len < 0 || n_rows < 0) return -1;
+  if (du_uvarint(buf, end, &pos, &block_size)) return -1;
+  if (du_uvarint(buf, end, &pos, &nmini)) return -1;
+  if (du_uvarint(buf, end, &pos, &total)) return -1;
+  if (du_uvarint(buf, end, &pos, &ufirst)) return -1;
+  if (nmini == 0 || block_size == 0 || block_size >= DL_MAX_BLOCK ||
+      block_size % nmini)
+    return -1;
+  const int64_t per_mini = (int64_t)(block_size / nmini);
+  if (per_mini % 32) return -1;
+  if (total > (uint64_t)n_rows) return -1;
+  pg[0] = (int64_t)((ufirst >> 1) ^ (~(ufirst & 1) + 1));
+  pg[1] = (int64_t)total;
+  pg[3] = out_base;
+  pg[4] = mb_begin;
+  int64_t remaining = total ? (int64_t)total - 1 : 0;
+  int64_t o = out_base + 1;
+  int64_t r = 0;
+  while (remaining > 0) {
+    uint64_t umin;
+    if (du_uvarint(buf, end, &pos, &umin)) return -1;
+    const int64_t min_delta = (int64_t)((umin >> 1) ^ (~(umin & 1) + 1));
+    if (pos + (int64_t)nmini > end) return -1;
+    const uint8_t* bws = buf + pos;
+    pos += (int64_t)nmini;
+    for (uint64_t i = 0; i < nmini && remaining > 0; i++) {
+      const int64_t bw = bws[i];
+      if (bw > 64) return -1;
+      const int64_t cnt = remaining < per_mini ? remaining : per_mini;
+      const int64_t need = (cnt * bw + 7) / 8;
+      if (pos + need > end) return -1;
+      if (r >= cap) return -1;
+      mb[4 * r + 0] = pos;
+      mb[4 * r + 1] = min_delta;
+      mb[4 * r + 2] = o;
+      mb[4 * r + 3] = bw | (cnt << 8) | (page_id << 32);
+      // a short last miniblock is padded to its nominal size; tolerate a
+      // writer that did not pad
+      pos += per_mini * bw / 8;
+      if (pos > end) pos = end;
+      o += cnt;
+      remaining -= cnt;
+      r++;
+    }
+  }
+  pg[2] = pos;
+  return r;
+}
+
+// LSB-first unpack of value j of a miniblock, as in k_pq_rle_idx: one
+// unaligned 8-byte word at bit>>3. The second word is read only when the
+// value straddles the first one; those bytes belong to the miniblock, so
+// no load goes beyond the staged buffer's 8-byte tail pad.
+__device__ __forceinline__ uint64_t dl_unpack(const uint8_t* __restrict__ p,
+                                              int64_t j, int bw,
+                                              uint64_t mask) {
+  if (bw == 0) return 0;
+  const int64_t bit = j * bw;
+  const uint8_t* q = p + (bit >> 3);
+  const int sh = (int)(bit & 7);
+  uint64_t w;
+  __builtin_memcpy(&w, q, 8);
+  uint64_t v = w >> sh;
+  if (sh + bw > 64) {  // implies sh >= 1
+    uint64_t w2;
+    __builtin_memcpy(&w2, q + 8, 8);
+    v |= w2 << (64 - sh);
+  }
+  return v & mask;
+}
+
+__global__ void k_pq_delta_sums(const DlMini* __restrict__ mb, int64_t nmb,
+                                const uint8_t* __restrict__ buf,
+                                uint64_t* __restrict__ sums) {
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t m = wave; m < nmb; m += nwaves) {  // wave-uniform
+    const DlMini d = mb[m];
+    const int bw = (int)(d.packed & 0xFF);
+    const int64_t count = (d.packed >> 8) & 0xFFFFFF;
+    const uint64_t mask = bw >= 64 ? ~0ull : ((1ull << bw) - 1);
+    const uint8_t* src = buf + d.byte_off;
+    unsigned long long s = 0;
+    for (int64_t j = lane; j < count; j += 64)
+      s += (uint64_t)d.min_delta + dl_unpack(src, j, bw, mask);
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if (lane == 0) sums[m] = s;
+  }
+}
+
+// In-place exclusive scan of the per-miniblock sums, one 256-thread block,
+// 8 entries per thread and round (the input is n/32 to n/64 entries).
+#define DL_SCAN_ITEMS 8
+__global__ void __launch_bounds__(256)
+k_pq_delta_scan(uint64_t* __restrict__ x, int64_t n) {
+  __shared__ uint64_t wtot[4];
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  uint64_t carry = 0;
+  for (int64_t c = 0; c < n; c += 256 * DL_SCAN_ITEMS) {  // block-uniform
+    const int64_t b = c + (int64_t)threadIdx.x * DL_SCAN_ITEMS;
+    uint64_t v[DL_SCAN_ITEMS];
+    unsigned long long tsum = 0;
+#pragma unroll
+    for (int k = 0; k < DL_SCAN_ITEMS; k++) {
+      v[k] = b + k < n ? x[b + k] : 0;
+      tsum += v[k];
+    }
+    unsigned long long incl = tsum;
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned long long t = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += t;
+    }
+    if (lane == 63) wtot[wv] = incl;
+    __syncthreads();
+    uint64_t woff = 0, round = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      if (w < wv) woff += wtot[w];
+      round += wtot[w];
+    }
+    uint64_t excl = carry + woff + (incl - tsum);
+#pragma unroll
+    for (int k = 0; k < DL_SCAN_ITEMS; k++) {
+      if (b + k < n) x[b + k] = excl;
+      excl += v[k];
+    }
+    carry += round;
+    __syncthreads();  // wtot is rewritten next round
+  }
+}
+
+template <typename T>
+__global__ void k_pq_delta_emit(const DlMini* __restrict__ mb, int64_t nmb,
+                                const DlPage* __restrict__ pg, int64_t npages,
+                                const uint8_t* __restrict__ buf,
+                                const uint64_t* __restrict__ excl,
+                                T* __restrict__ out) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  const int lane = threadIdx.x & 63;
+  for (int64_t m = tid >> 6; m < nmb; m += nthreads >> 6) {  // wave-uniform
+    const DlMini d = mb[m];
+    const int bw = (int)(d.packed & 0xFF);
+    const int64_t count = (d.packed >> 8) & 0xFFFFFF;
+    const DlPage p = pg[d.packed >> 32];
+    const uint64_t mask = bw >= 64 ? ~0ull : ((1ull << bw) - 1);
+    const uint8_t* src = buf + d.byte_off;
+    uint64_t carry = (uint64_t)p.first + (excl[m] - excl[p.mb_begin]);
+    for (int64_t s = 0; s < count; s += 64) {  // 64-lane strips
+      const int64_t j = s + lane;
+      unsigned long long incl =
+          j < count ? (uint64_t)d.min_delta + dl_unpack(src, j, bw, mask) : 0;
+      for (int k = 1; k < 64; k <<= 1) {
+        const unsigned long long t = __shfl_up(incl, k, 64);
+        if (lane >= k) incl += t;
+      }
+      if (j < count) out[d.out_idx + j] = (T)(carry + incl);
+      carry += __shfl(incl, 63, 64);
+    }
+  }
+  // every page's first value, pages without any miniblock included
+  for (int64_t i = tid; i < npages; i += nthreads) {
+    const DlPage p = pg[i];
+    if (p.total > 0) out[p.out_base] = (T)(uint64_t)p.first;
+  }
+}
+
+static inline int dl_grid(int64_t nmb) {
+  int64_t g = (nmb * 64 + 255) / 256;
+  if (g > 2048) g = 2048;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
+AU_EXPORT int au_pq_delta_sums(const void* mb_dev, int64_t nmb,
+                               const void* buf, void* sums, void* stream) {
+  if (nmb <= 0) return 0;
+  hipLaunchKernelGGL(k_pq_delta_sums, dim3(dl_grid(nmb)), dim3(256), 0,
+                     (hipStream_t)stream, (const DlMini*)mb_dev, nmb,
+                     (const uint8_t*)buf, (uint64_t*)sums);
+  return (int)hipGetLastError();
+}
+
+AU_EXPORT int au_pq_delta_scan(void* sums, int64_t nmb, void* stream) {
+  if (nmb <= 0) return 0;
+  hipLaunchKernelGGL(k_pq_delta_scan, dim3(1), dim3(256), 0,
+                     (hipStream_t)stream, (uint64_t*)sums, nmb);
+  return (int)hipGetLastError();
+}
+
+// `out` holds the compact per-present-value array: int32 (esize 4, low 32
+// bits of each value) or int64 (esize 8).
+AU_EXPORT int au_pq_delta_emit(const void* mb_dev, int64_t nmb,
+                               const void* pg_dev, int64_t npages,
+                               const void* buf, const void* excl, void* out,
+                               int esize, void* stream) {
+  if (npages <= 0) return 0;
+  if (esize != 4 && esize != 8) return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 g(dl_grid(nmb)), b(256);
+  if (esize == 4)
+    hipLaunchKernelGGL((k_pq_delta_emit<uint32_t>), g, b, 0, s,
+                       (const DlMini*)mb_dev, nmb, (const DlPage*)pg_dev,
+                       npages, (const uint8_t*)buf, (const uint64_t*)excl,
+                       (uint32_t*)out);
+  else
+    hipLaunchKernelGGL((k_pq_delta_emit<uint64_t>), g, b, 0, s,
+                       (const DlMini*)mb_dev, nmb, (const DlPage*)pg_dev,
+                       npages, (const uint8_t*)buf, (const uint64_t*)excl,
+                       (uint64_t*)out);
+  return (int)hipGetLastError();
 }

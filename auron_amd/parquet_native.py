@@ -12,10 +12,16 @@ host path per column.
 Supported fast path: data pages v1+v2, UNCOMPRESSED/snappy/zstd/gzip
 chunks (host page decompression into the staging buffer's extra
 region), optional-level (max_def_level<=1) columns; PLAIN,
-RLE_DICTIONARY and DELTA_BINARY_PACKED (host delta unpack -> PLAIN)
-INT32/INT64/FLOAT/DOUBLE; BYTE_ARRAY strings both dictionary-encoded
-(dictionary page parsed host-side, per-row bytes gathered on device)
-and PLAIN (host offset walk, device byte gather).
+and RLE_DICTIONARY INT32/INT64/FLOAT/DOUBLE; DELTA_BINARY_PACKED
+INT32/INT64 (the host indexes the block/miniblock headers once per file,
+the k_pq_delta_* kernels unpack and prefix-sum the values, one wave per
+miniblock); BYTE_ARRAY strings dictionary-encoded (dictionary page
+parsed host-side, per-row bytes gathered on device), PLAIN (host offset
+walk, device byte gather) and DELTA_LENGTH_BYTE_ARRAY (lengths decoded by
+the same delta kernels, device byte gather). With
+spark.auron.scan.deltaNative.enable off, DELTA_BINARY_PACKED pages are
+expanded to PLAIN by a host job per page and DELTA_LENGTH_BYTE_ARRAY
+columns fall back to pyarrow. DELTA_BYTE_ARRAY always falls back.
 """
 from __future__ import annotations
 
@@ -154,7 +160,9 @@ class PageDesc:
     values_off: int  # byte offset of values ([bw][rle-indices] for dict pages)
     values_len: int
     row_start: int
-    encoding: int = 0  # 0=PLAIN, 8=RLE_DICTIONARY (PLAIN_DICTIONARY folded in)
+    # 0=PLAIN, 8=RLE_DICTIONARY (PLAIN_DICTIONARY folded in),
+    # 5=DELTA_BINARY_PACKED, 6=DELTA_LENGTH_BYTE_ARRAY (device-decoded)
+    encoding: int = 0
 
 
 @dataclass
@@ -178,6 +186,9 @@ class ChunkPages:
     # (absolute offset, byte length) in page order
     plain_str_offs: Optional[np.ndarray] = None
     plain_str_lens: Optional[np.ndarray] = None
+    # host-built DELTA_BINARY_PACKED block/miniblock index of all pages
+    # (delta_index); cached so HBM-cache hits never need the host buffer
+    delta_idx: Optional["DeltaIndex"] = None
 
     @property
     def is_dict(self) -> bool:
@@ -226,13 +237,26 @@ def _codec_decompress(codec: str, raw: bytes, ulen: int) -> bytes:
 def parse_pages(buf: np.ndarray, chunk_off: int, chunk_len: int,
                 num_values: int, has_def: bool, codec: Optional[str] = None,
                 extra: Optional[_ExtraAlloc] = None,
-                esize: int = 0) -> Optional[ChunkPages]:
+                esize: int = 0, phys: str = "",
+                delta_native: bool = False) -> Optional[ChunkPages]:
     """Parse page headers of one column chunk (v1 + v2 data pages).
 
     Supports PLAIN data pages and RLE_DICTIONARY/PLAIN_DICTIONARY data
     pages with a PLAIN dictionary page; snappy/zstd/gzip page payloads
     are routed through the extra-region decompress jobs. Chunks mixing
-    dictionary and plain data pages fall back to the host path."""
+    dictionary and plain data pages fall back to the host path.
+
+    With `delta_native`, DELTA_BINARY_PACKED pages of INT32/INT64 chunks
+    and DELTA_LENGTH_BYTE_ARRAY pages of BYTE_ARRAY chunks keep their
+    encoding (5 / 6) for the device decode; without it encoding 5 becomes
+    a host "delta" job that expands the page to PLAIN, and encoding 6 is
+    rejected."""
+    delta_encs = ()
+    if delta_native:
+        if phys in ("INT32", "INT64"):
+            delta_encs = (5,)
+        elif phys == "BYTE_ARRAY":
+            delta_encs = (6,)
     mv = memoryview(buf)
     pos = chunk_off
     end = chunk_off + chunk_len
@@ -273,10 +297,14 @@ def parse_pages(buf: np.ndarray, chunk_off: int, chunk_len: int,
                 1: "num_values", 4: "encoding", 5: "def_len", 6: "rep_len",
                 7: "is_compressed"})
             enc = dph.get("encoding", 0)
+            host_delta = False
             if enc in (2, 8):
                 enc = 8
-            elif enc == 5 and esize in (4, 8) and extra is not None:
-                pass  # DELTA_BINARY_PACKED: host-decoded to PLAIN below
+            elif enc in delta_encs:
+                pass  # keeps its encoding: decoded from the host-built index
+            elif enc == 5 and not delta_native and esize in (4, 8) \
+                    and extra is not None:
+                host_delta = True  # host-decoded to PLAIN below
             elif enc != 0:
                 return None
             nv = dph["num_values"]
@@ -298,7 +326,7 @@ def parse_pages(buf: np.ndarray, chunk_off: int, chunk_len: int,
                 def_off = page_data if dlen else -1
                 values_off = vals_raw
                 values_len = vals_clen
-            if enc == 5:
+            if host_delta:
                 values_off = extra.delta(values_off, values_len, nv, esize)
                 values_len = nv * esize
                 enc = 0
@@ -315,12 +343,16 @@ def parse_pages(buf: np.ndarray, chunk_off: int, chunk_len: int,
         dph, _ = _read_struct_fields(mv, dph_range[0], {
             1: "num_values", 2: "encoding", 3: "def_enc", 4: "rep_enc"})
         enc = dph.get("encoding", 0)
+        host_delta = False
         if enc in (2, 8):
             enc = 8
             if ck.dict_off < 0:
                 return None
-        elif enc == 5 and esize in (4, 8) and extra is not None:
-            pass  # DELTA_BINARY_PACKED: host-decoded to PLAIN below
+        elif enc in delta_encs:
+            pass  # keeps its encoding: decoded from the host-built index
+        elif enc == 5 and not delta_native and esize in (4, 8) \
+                and extra is not None:
+            host_delta = True  # host-decoded to PLAIN below
         elif enc != 0:
             return None
         nv = dph["num_values"]
@@ -344,7 +376,7 @@ def parse_pages(buf: np.ndarray, chunk_off: int, chunk_len: int,
                                      row, enc))
         else:
             ck.pages.append(PageDesc(nv, -1, 0, page_data, page_len, row, enc))
-        if enc == 5:
+        if host_delta:
             p = ck.pages[-1]
             dest = extra.delta(p.values_off, p.values_len, nv, esize)
             ck.pages[-1] = PageDesc(p.n_values, p.def_off, p.def_len, dest,
@@ -358,6 +390,8 @@ def parse_pages(buf: np.ndarray, chunk_off: int, chunk_len: int,
         return None
     if encs == {8} and ck.dict_off < 0:
         return None
+    if encs & {5, 6} and ck.dict_off >= 0:
+        return None  # dictionary page + delta data pages -> host fallback
     return ck
 
 
@@ -458,6 +492,208 @@ def parse_plain_strings(buf: np.ndarray, ck: ChunkPages) -> None:
         n += got
     ck.plain_str_offs = offs[:n]
     ck.plain_str_lens = lens[:n].astype(np.int64)
+
+
+# ------------------------------------------------- DELTA_BINARY_PACKED
+# present values decoded per path: DELTA_BINARY_PACKED columns by the
+# k_pq_delta_* kernels / on the host (delta_decode_ref on CPU reads,
+# au_host_delta_unpack jobs with the switch off), and strings whose
+# DELTA_LENGTH_BYTE_ARRAY lengths went through the delta decode
+STATS = {"delta_values_device": 0, "delta_values_host": 0,
+         "delta_length_strings": 0}
+
+
+def delta_native_enabled() -> bool:
+    from .config import SCAN_DELTA_NATIVE, AuronConf
+
+    return bool(AuronConf().get(SCAN_DELTA_NATIVE))
+
+
+@dataclass
+class DeltaIndex:
+    """Block/miniblock descriptors of the DELTA_BINARY_PACKED streams of a
+    chunk's pages (layout: csrc/parquet.hip, DlPage / DlMini).
+
+    pg[P,5] int64: first value, header total, absolute stream-end byte,
+    compact output index of the first value, first miniblock row in `mb`.
+    mb[M,4] int64, miniblocks that hold values only: absolute byte offset
+    of the bit data, min_delta, compact output index of its first value,
+    bit width | values held << 8 | page << 32."""
+    pg: np.ndarray
+    mb: np.ndarray
+    total: int  # present values over all pages
+    last_byte: int  # one past the last bit-data byte any miniblock reads
+
+    def mb_fields(self):
+        packed = self.mb[:, 3]
+        return packed & 0xFF, (packed >> 8) & 0xFFFFFF, packed >> 32
+
+
+def delta_index(buf: np.ndarray, pages) -> DeltaIndex:
+    """Index the DELTA_BINARY_PACKED streams at `pages`, a list of
+    (values_off, values_len, n_rows), with au_host_delta_index: headers
+    only, no values. Raises ValueError on a corrupt stream."""
+    from . import native
+
+    lib = native.host_lib()
+    buf = np.ascontiguousarray(buf)
+    npages = len(pages)
+    cap = sum(int(n) // 32 + 2 for (_o, _l, n) in pages)
+    pg = np.zeros((npages, 5), dtype=np.int64)
+    mb = np.zeros((cap, 4), dtype=np.int64)
+    base = buf.ctypes.data
+    out = 0
+    m = 0
+    for i, (off, ln, n_rows) in enumerate(pages):
+        if off < 0 or ln < 0 or off + ln > buf.size:
+            raise ValueError("corrupt DELTA_BINARY_PACKED page")
+        got = lib.au_host_delta_index(
+            base, off, ln, n_rows, out, i, m, pg.ctypes.data + 40 * i,
+            mb.ctypes.data + 32 * m, cap - m)
+        if got < 0:
+            raise ValueError("corrupt DELTA_BINARY_PACKED page")
+        m += got
+        out += int(pg[i, 1])
+    mb = np.ascontiguousarray(mb[:m])
+    last = 0
+    if m:
+        bw = mb[:, 3] & 0xFF
+        cnt = (mb[:, 3] >> 8) & 0xFFFFFF
+        last = int((mb[:, 0] + (cnt * bw + 7) // 8).max())
+    return DeltaIndex(pg, mb, out, last)
+
+
+_DELTA_REF_BITS = 1 << 25  # unpacked bits per numpy batch
+
+
+def delta_decode_ref(buf: np.ndarray, index: DeltaIndex,
+                     esize: int) -> np.ndarray:
+    """numpy decode of an indexed chunk -> compact per-present-value array
+    (int32: low 32 bits, or int64). Same descriptors, 64-bit wrap and
+    truncation as the kernels; oracle for them and the CPU read path."""
+    total = index.total
+    acc = np.zeros(total, dtype=np.uint64)
+    pg, mb = index.pg, index.mb
+    if len(mb):
+        bws, cnts, _pages = index.mb_fields()
+        shape = bws * (1 << 24) + cnts
+        for key in np.unique(shape):
+            bw, cnt = int(key >> 24), int(key & 0xFFFFFF)
+            rows = np.nonzero(shape == key)[0]
+            nbytes = (cnt * bw + 7) // 8
+            step = max(1, _DELTA_REF_BITS // max(cnt * max(bw, 1), 1))
+            for s in range(0, len(rows), step):
+                r = rows[s:s + step]
+                vals = np.zeros((len(r), cnt), dtype=np.uint64)
+                if bw:
+                    src = mb[r, 0][:, None] + np.arange(nbytes, dtype=np.int64)
+                    bits = np.unpackbits(buf[src], axis=1, bitorder="little")
+                    bits = bits[:, :cnt * bw].reshape(len(r), cnt, bw)
+                    for k in range(bw):
+                        vals |= bits[:, :, k].astype(np.uint64) << np.uint64(k)
+                vals += mb[r, 1].astype(np.uint64)[:, None]
+                dst = mb[r, 2][:, None] + np.arange(cnt, dtype=np.int64)
+                acc[dst] = vals
+    live = pg[:, 1] > 0
+    acc[pg[live, 3]] = pg[live, 0].astype(np.uint64)
+    run = np.cumsum(acc, dtype=np.uint64)
+    # restart at every page: subtract the running sum before its first value
+    before = np.zeros(len(pg), dtype=np.uint64)
+    starts = pg[live, 3]
+    before[live] = np.where(starts > 0, run[np.maximum(starts - 1, 0)],
+                            np.uint64(0))
+    out = run - np.repeat(before, pg[:, 1])
+    if esize == 4:
+        return out.astype(np.uint32).view(np.int32)
+    if esize == 8:
+        return out.view(np.int64)
+    raise ValueError(f"delta esize {esize}")
+
+
+def delta_decode(dbuf: torch.Tensor, index: DeltaIndex, esize: int, device,
+                 capacity: int = 0) -> torch.Tensor:
+    """Device decode of an indexed chunk (k_pq_delta_sums -> scan ->
+    k_pq_delta_emit) -> compact per-present-value tensor, int32 or int64.
+    `capacity` over-allocates the backing storage (the returned view still
+    has index.total elements) so a later null scatter of a page whose def
+    levels disagree with its header cannot read past the allocation."""
+    from . import native
+
+    lib = native.require()
+    if esize not in (4, 8):
+        raise ValueError(f"delta esize {esize}")
+    # the kernels check nothing: every unpack word must lie inside dbuf
+    if len(index.mb) and dbuf.numel() < index.last_byte + 8:
+        raise ValueError(
+            f"staged buffer of {dbuf.numel()} bytes lacks the 8-byte pad "
+            f"past indexed byte {index.last_byte}")
+    tdt = torch.int32 if esize == 4 else torch.int64
+    store = torch.empty(max(index.total, capacity, 1), dtype=tdt,
+                        device=device)
+    out = store[:index.total]
+    if index.total == 0:
+        return out
+    sp = native.stream_ptr(device)
+    nmb = len(index.mb)
+    dpg = _pin_to_device(index.pg.reshape(-1), device)
+    dmb = sums = None
+    if nmb:
+        dmb = _pin_to_device(index.mb.reshape(-1), device)
+        sums = torch.empty(nmb, dtype=torch.int64, device=device)
+        rc = lib.au_pq_delta_sums(dmb.data_ptr(), nmb, dbuf.data_ptr(),
+                                  sums.data_ptr(), sp)
+        native.check(rc, "au_pq_delta_sums")
+        rc = lib.au_pq_delta_scan(sums.data_ptr(), nmb, sp)
+        native.check(rc, "au_pq_delta_scan")
+    rc = lib.au_pq_delta_emit(dmb.data_ptr() if nmb else None, nmb,
+                              dpg.data_ptr(), len(index.pg), dbuf.data_ptr(),
+                              sums.data_ptr() if nmb else None,
+                              out.data_ptr(), esize, sp)
+    native.check(rc, "au_pq_delta_emit")
+    return out
+
+
+def _chunk_delta_index(buf: np.ndarray, ck: ChunkPages) -> None:
+    if ck.delta_idx is None:
+        ck.delta_idx = delta_index(
+            buf, [(p.values_off, p.values_len, p.n_values) for p in ck.pages])
+
+
+def _validity_np(buf: np.ndarray, pages: List[PageDesc],
+                 num_values: int) -> Optional[np.ndarray]:
+    if pages[0].def_off < 0:
+        return None
+    validity = np.zeros(num_values, dtype=np.uint8)
+    for p in pages:
+        validity[p.row_start:p.row_start + p.n_values] = rle1_decode_np(
+            buf[p.def_off:p.def_off + p.def_len], p.n_values)
+    return validity
+
+
+def _check_delta_counts(ck: ChunkPages, validity: Optional[np.ndarray]):
+    """Each page's header total must equal its present-value count."""
+    for p, total in zip(ck.pages, ck.delta_idx.pg[:, 1]):
+        want = p.n_values if validity is None else \
+            int(validity[p.row_start:p.row_start + p.n_values].sum())
+        if int(total) != want:
+            raise ValueError("corrupt DELTA_BINARY_PACKED page: header "
+                             f"holds {int(total)} values, levels say {want}")
+
+
+def decode_chunk_np_delta(buf: np.ndarray, ck: ChunkPages, num_values: int,
+                          phys: str):
+    """Host decoder for DELTA_BINARY_PACKED chunks (delta_decode_ref)."""
+    npdt = _PHYS_NP[phys]
+    _chunk_delta_index(buf, ck)
+    compact = delta_decode_ref(buf, ck.delta_idx, npdt().itemsize)
+    validity = _validity_np(buf, ck.pages, num_values)
+    _check_delta_counts(ck, validity)
+    STATS["delta_values_host"] += ck.delta_idx.total
+    if validity is None:
+        return compact, None
+    out = np.zeros(num_values, dtype=npdt)
+    out[validity.astype(bool)] = compact
+    return out, validity
 
 
 def _chunk_indices_np(buf: np.ndarray, ck: ChunkPages,
@@ -685,6 +921,8 @@ class _FileMeta:
     extra_total: int = 0  # decompressed-page region size (after raw+pad)
     jobs: list = None  # decompress/copy jobs refilled per read
     runs_parsed: bool = False  # def-level run headers host-parsed
+    delta_native: bool = True  # spark.auron.scan.deltaNative.enable at build
+    delta_indexed: bool = False  # delta streams host-indexed (delta_index)
 
 
 def _build_meta(path: str, columns: List[str]) -> Optional[_FileMeta]:
@@ -730,10 +968,15 @@ def _build_meta(path: str, columns: List[str]) -> Optional[_FileMeta]:
 
 
 def _get_meta(path: str, columns: List[str]) -> Optional[_FileMeta]:
-    key = (path, os.path.getmtime(path), tuple(columns))
+    # the delta switch decides how pages are parsed, so it is part of the
+    # key: flipping it inside a process never meets a stale parse
+    dn = delta_native_enabled()
+    key = (path, os.path.getmtime(path), tuple(columns), dn)
     if key in _META_CACHE:
         return _META_CACHE[key]
     meta = _build_meta(path, columns)
+    if meta is not None:
+        meta.delta_native = dn
     if len(_META_CACHE) > _META_CACHE_MAX:
         _META_CACHE.clear()
     _META_CACHE[key] = meta
@@ -774,7 +1017,17 @@ def _decode_all(meta, buf, dbuf, device, use_gpu):
         any_nulls = False
         for (chunk, ck) in zip(cm.chunks, cm.pages):
             (_off, _clen, nvals, chunk_nulls, _codec) = chunk
-            if use_gpu:
+            if ck.pages[0].encoding == 5:
+                if use_gpu:
+                    data_t, valid_t = _decode_chunk_gpu_delta(
+                        dbuf, ck, nvals, cm.phys, device, chunk_nulls)
+                else:
+                    data_np, valid_np = decode_chunk_np_delta(buf, ck, nvals,
+                                                              cm.phys)
+                    data_t = torch.from_numpy(data_np)
+                    valid_t = torch.from_numpy(valid_np).to(torch.bool) \
+                        if valid_np is not None else None
+            elif use_gpu:
                 if ck.is_dict:
                     data_t, valid_t = _decode_chunk_gpu_dict(
                         dbuf, buf, ck, nvals, cm.phys, device, chunk_nulls)
@@ -830,7 +1083,8 @@ def read_columns_native(path: str, columns: List[str], device,
     use_gpu = (not _np_only) and torch.device(device).type == "cuda"
 
     if use_gpu and meta.parsed and getattr(meta, "runs_parsed", False):
-        ck_key = (path, os.path.getmtime(path), tuple(columns))
+        ck_key = (path, os.path.getmtime(path), tuple(columns),
+                  meta.delta_native)
         hit = _dbuf_cache_get(ck_key)
         if hit is not None:
             return _decode_all(meta, None, hit, device, True)
@@ -859,6 +1113,7 @@ def read_columns_native(path: str, columns: List[str], device,
                     buf.ctypes.data + dest)
                 if got < 0 or got > nv:
                     raise ValueError("corrupt DELTA_BINARY_PACKED page")
+                STATS["delta_values_host"] += int(got)
             else:
                 _, s0, n, dest = job
                 buf[dest:dest + n] = buf[s0:s0 + n]
@@ -884,7 +1139,8 @@ def read_columns_native(path: str, columns: List[str], device,
                     es = _PHYS_NP[cm.phys]().itemsize \
                         if cm.phys in _PHYS_NP else 0
                     ck = parse_pages(buf, new_off, clen, nvals, cm.has_def,
-                                     codec, extra, esize=es)
+                                     codec, extra, esize=es, phys=cm.phys,
+                                     delta_native=meta.delta_native)
                     if ck is None:
                         good = False
                         break
@@ -913,6 +1169,16 @@ def read_columns_native(path: str, columns: List[str], device,
         if meta.jobs:
             run_jobs(buf, meta.jobs)
 
+        if not meta.delta_indexed:
+            # one-time host walk of the delta block/miniblock headers, for
+            # CPU and GPU reads alike; after the decompression jobs, like
+            # the def-level runs below
+            for cm in meta.cols:
+                for ck in cm.pages:
+                    if ck.pages[0].encoding in (5, 6):
+                        _chunk_delta_index(buf, ck)
+            meta.delta_indexed = True
+
         if use_gpu and not meta.runs_parsed:
             # one-time host parse of def-level run headers (see
             # _parse_rle1_runs); must run after decompression jobs so
@@ -933,12 +1199,12 @@ def read_columns_native(path: str, columns: List[str], device,
                     if cm.phys == "BYTE_ARRAY":
                         if ck.is_dict:
                             parse_dict_strings(buf, ck)
-                        else:
+                        elif ck.pages[0].encoding != 6:
                             parse_plain_strings(buf, ck)
                     if ck.is_dict and ck.idx_bws is None:
                         ck.idx_bws = [int(buf[p.values_off]) for p in ck.pages]
-            _dbuf_cache_put((path, os.path.getmtime(path), tuple(columns)),
-                            dbuf)
+            _dbuf_cache_put((path, os.path.getmtime(path), tuple(columns),
+                             meta.delta_native), dbuf)
 
         return _decode_all(meta, buf, dbuf, device, use_gpu)
     finally:
@@ -1056,6 +1322,33 @@ def _decode_chunk_gpu_dict(dbuf, buf, ck: ChunkPages, num_values: int,
     return out, vmask
 
 
+def _strings_tail_np(buf, str_offs: np.ndarray, str_lens: np.ndarray,
+                     validity: Optional[np.ndarray], num_values: int,
+                     chunk_nulls: bool) -> Column:
+    """Host tail of the non-dictionary string paths: per-PRESENT-value
+    (absolute offset, length) -> offsets + gathered bytes."""
+    vmask = validity.astype(bool) if validity is not None \
+        else np.ones(num_values, dtype=bool)
+    lens = np.zeros(num_values, dtype=np.int64)
+    lens[vmask] = str_lens
+    starts = np.zeros(num_values, dtype=np.int64)
+    starts[vmask] = str_offs
+    offsets = np.zeros(num_values + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    data = np.empty(int(offsets[-1]), dtype=np.uint8)
+    pos = 0
+    for r in range(num_values):
+        ln = lens[r]
+        if ln:
+            data[pos:pos + ln] = buf[starts[r]:starts[r] + ln]
+            pos += ln
+    vt = None
+    if validity is not None and chunk_nulls and not validity.all():
+        vt = torch.from_numpy(validity.astype(bool))
+    return Column(dtypes.string, torch.from_numpy(data), vt,
+                  torch.from_numpy(offsets))
+
+
 def _decode_chunk_plain_strings(buf, dbuf, ck: ChunkPages, num_values: int,
                                 device, use_gpu: bool,
                                 chunk_nulls: bool) -> Column:
@@ -1064,39 +1357,91 @@ def _decode_chunk_plain_strings(buf, dbuf, ck: ChunkPages, num_values: int,
     overflows the dictionary-page limit — high-cardinality strings)."""
     if not use_gpu:
         parse_plain_strings(buf, ck)
-        has_def = ck.pages[0].def_off >= 0
-        validity = None
-        if has_def:
-            validity = np.zeros(num_values, dtype=np.uint8)
-            for p in ck.pages:
-                validity[p.row_start:p.row_start + p.n_values] = rle1_decode_np(
-                    buf[p.def_off:p.def_off + p.def_len], p.n_values)
-        vmask = validity.astype(bool) if validity is not None \
-            else np.ones(num_values, dtype=bool)
-        lens = np.zeros(num_values, dtype=np.int64)
-        lens[vmask] = ck.plain_str_lens
-        starts = np.zeros(num_values, dtype=np.int64)
-        starts[vmask] = ck.plain_str_offs
-        offsets = np.zeros(num_values + 1, dtype=np.int64)
-        np.cumsum(lens, out=offsets[1:])
-        data = np.empty(int(offsets[-1]), dtype=np.uint8)
-        pos = 0
-        for r in range(num_values):
-            ln = lens[r]
-            if ln:
-                data[pos:pos + ln] = buf[starts[r]:starts[r] + ln]
-                pos += ln
-        vt = None
-        if validity is not None and chunk_nulls and not validity.all():
-            vt = torch.from_numpy(validity.astype(bool))
-        return Column(dtypes.string, torch.from_numpy(data), vt,
-                      torch.from_numpy(offsets))
+        validity = _validity_np(buf, ck.pages, num_values)
+        return _strings_tail_np(buf, ck.plain_str_offs, ck.plain_str_lens,
+                                validity, num_values, chunk_nulls)
     validity, prefix = _gpu_validity_prefix(dbuf, ck.pages, num_values, device,
                                             chunk_nulls, ck.runs_np)
     if ck.plain_str_offs is None:
         parse_plain_strings(buf, ck)
     offs_t = torch.from_numpy(ck.plain_str_offs).to(device, non_blocking=True)
     lens_t = torch.from_numpy(ck.plain_str_lens).to(device, non_blocking=True)
+    return _strings_tail_gpu(dbuf, offs_t, lens_t, validity, prefix,
+                             num_values, device, chunk_nulls)
+
+
+def _decode_chunk_delta_strings(buf, dbuf, ck: ChunkPages, num_values: int,
+                                device, use_gpu: bool,
+                                chunk_nulls: bool) -> Column:
+    """DELTA_LENGTH_BYTE_ARRAY chunk -> string Column. A page is the
+    DELTA_BINARY_PACKED lengths followed by the strings' bytes back to
+    back: a value starts at the page's stream end plus the exclusive sum
+    of the lengths before it, and the lengths of a page must add up to
+    exactly the bytes left in it."""
+    idx = ck.delta_idx
+    pg = idx.pg
+    page_bytes = np.array([p.values_off + p.values_len for p in ck.pages],
+                          dtype=np.int64) - pg[:, 2]
+    if not use_gpu:
+        lens = delta_decode_ref(buf, idx, 4).astype(np.int64)
+        validity = _validity_np(buf, ck.pages, num_values)
+        _check_delta_counts(ck, validity)
+        run = np.cumsum(lens)
+        excl = run - lens
+        live = pg[:, 1] > 0
+        first = np.zeros(len(pg), dtype=np.int64)
+        first[live] = excl[pg[live, 3]]
+        sums = np.zeros(len(pg), dtype=np.int64)
+        sums[live] = run[pg[live, 3] + pg[live, 1] - 1] - first[live]
+        if (lens < 0).any() or (sums != page_bytes).any():
+            raise ValueError("corrupt DELTA_LENGTH_BYTE_ARRAY page: lengths "
+                             "do not add up to the page's bytes")
+        starts = excl + np.repeat(pg[:, 2] - first, pg[:, 1])
+        STATS["delta_length_strings"] += idx.total
+        return _strings_tail_np(buf, starts, lens, validity, num_values,
+                                chunk_nulls)
+    validity, prefix = _gpu_validity_prefix(dbuf, ck.pages, num_values, device,
+                                            chunk_nulls, ck.runs_np)
+    if validity is None and idx.total != num_values:
+        raise ValueError("corrupt DELTA_LENGTH_BYTE_ARRAY page: header "
+                         "totals disagree with the row count")
+    lens_t = delta_decode(dbuf, idx, 4, device).to(torch.int64)
+    n = idx.total
+    # per-page constants, one small upload: stream end, compact base,
+    # index of the last value, bytes left after the stream, live flag
+    live = pg[:, 1] > 0
+    consts = np.stack([pg[:, 2], np.minimum(pg[:, 3], max(n - 1, 0)),
+                       np.clip(pg[:, 3] + pg[:, 1] - 1, 0, max(n - 1, 0)),
+                       page_bytes, live.astype(np.int64), pg[:, 1]])
+    dc = _pin_to_device(consts.reshape(-1), device).view(torch.int64) \
+        .view(6, len(pg))
+    if n:
+        run = torch.cumsum(lens_t, 0)
+        excl = run - lens_t
+        first = excl[dc[1]]
+        sums = (run[dc[2]] - first) * dc[4]
+        pid = torch.repeat_interleave(
+            torch.arange(len(pg), dtype=torch.int64, device=device), dc[5],
+            output_size=n)
+        offs_t = excl + (dc[0] - first)[pid]
+        bad = (sums != dc[3]).any() | (lens_t < 0).any()
+    else:  # all-NULL chunk: one dummy entry for the clamped row lookup
+        offs_t = lens_t = torch.zeros(1, dtype=torch.int64, device=device)
+        bad = torch.from_numpy(page_bytes != 0).any().to(device)
+    if prefix is not None:
+        bad = bad | (prefix[-1] != n)
+    STATS["delta_length_strings"] += n
+    return _strings_tail_gpu(dbuf, offs_t, lens_t, validity, prefix,
+                             num_values, device, chunk_nulls, bad)
+
+
+def _strings_tail_gpu(dbuf, offs_t, lens_t, validity, prefix, num_values: int,
+                      device, chunk_nulls: bool, bad=None) -> Column:
+    """Device tail of the non-dictionary string paths: compact per-PRESENT
+    value (absolute offset, length) int64 tensors -> validity routing,
+    offsets, byte gather. `bad` is an optional device flag checked in the
+    one sync this path does anyway (offsets[-1]), before any byte is
+    gathered."""
     if validity is not None:
         vmask = validity.to(torch.bool)
         pos = (prefix - 1).clamp(min=0)
@@ -1108,9 +1453,18 @@ def _decode_chunk_plain_strings(buf, dbuf, ck: ChunkPages, num_values: int,
         vmask = None
         lens = lens_t[:num_values]
         starts = offs_t[:num_values]
+    if bad is not None:
+        # a bad length could be negative: keep it out of the cumsum
+        lens = torch.where(bad, torch.zeros_like(lens), lens)
     offsets = torch.zeros(num_values + 1, dtype=torch.int64, device=device)
     torch.cumsum(lens, 0, out=offsets[1:])
-    total = int(offsets[-1].item())
+    if bad is not None:
+        total, is_bad = torch.stack([offsets[-1], bad.to(torch.int64)]).tolist()
+        if is_bad:
+            raise ValueError("corrupt DELTA_LENGTH_BYTE_ARRAY page: lengths "
+                             "do not add up to the page's bytes")
+    else:
+        total = int(offsets[-1].item())
     if total:
         row = torch.repeat_interleave(lens)
         within = torch.arange(total, dtype=torch.int64, device=device) \
@@ -1126,6 +1480,9 @@ def _decode_chunk_plain_strings(buf, dbuf, ck: ChunkPages, num_values: int,
 def _decode_chunk_strings(buf, dbuf, ck: ChunkPages, num_values: int, device,
                           use_gpu: bool, chunk_nulls: bool) -> Column:
     """Dictionary-encoded BYTE_ARRAY chunk -> string Column."""
+    if ck.pages[0].encoding == 6:
+        return _decode_chunk_delta_strings(buf, dbuf, ck, num_values, device,
+                                           use_gpu, chunk_nulls)
     if not ck.is_dict:
         return _decode_chunk_plain_strings(buf, dbuf, ck, num_values, device,
                                            use_gpu, chunk_nulls)
@@ -1166,6 +1523,43 @@ def _decode_chunk_strings(buf, dbuf, ck: ChunkPages, num_values: int, device,
         data = torch.empty(0, dtype=torch.uint8, device=device)
     vt = vmask if (vmask is not None and chunk_nulls) else None
     return Column(dtypes.string, data, vt, offsets.to(torch.int64))
+
+
+def _decode_chunk_gpu_delta(dbuf: torch.Tensor, ck: ChunkPages,
+                            num_values: int, phys: str, device,
+                            chunk_nulls: bool = True):
+    """DELTA_BINARY_PACKED chunk on device: the delta kernels produce the
+    compact per-present-value array, which then plays the role of PLAIN
+    page bytes for the existing null scatter. No host sync: the header
+    totals in the index give every count the host needs."""
+    from . import native
+
+    lib = native.require()
+    idx = ck.delta_idx
+    pages = ck.pages
+    esize = _PHYS_NP[phys]().itemsize
+    has_def = pages[0].def_off >= 0 and chunk_nulls
+    compact = delta_decode(dbuf, idx, esize, device, capacity=num_values)
+    STATS["delta_values_device"] += idx.total
+    if not has_def:
+        if idx.total != num_values:
+            raise ValueError("corrupt DELTA_BINARY_PACKED page: header "
+                             "totals disagree with the row count")
+        return compact, None
+    validity, prefix = _gpu_validity_prefix(dbuf, pages, num_values, device,
+                                            True, ck.runs_np)
+    arr = np.zeros((len(pages), 6), dtype=np.int64)
+    for i, p in enumerate(pages):
+        arr[i] = (p.def_off, p.def_len, int(idx.pg[i, 3]) * esize, p.n_values,
+                  p.row_start, 0)
+    darr = _pin_to_device(arr.reshape(-1), device)
+    out = torch.empty(num_values, dtype=compact.dtype, device=device)
+    rc = lib.au_pq_scatter(darr.data_ptr(), len(pages), compact.data_ptr(),
+                           validity.data_ptr(), prefix.data_ptr(),
+                           out.data_ptr(), esize, num_values,
+                           native.stream_ptr(device))
+    native.check(rc, "au_pq_scatter")
+    return out, validity.to(torch.bool)
 
 
 def _decode_chunk_gpu(dbuf: torch.Tensor, pages: List[PageDesc], num_values: int,
