@@ -395,6 +395,28 @@ def compact_validity(v: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     return None if bool(v.all()) else v
 
 
+def adjacent_equal(c: Column, nan_equal: bool = False) -> torch.Tensor:
+    """eq mask between row i and i-1, for rows 1..n-1 (null==null;
+    NaN==NaN only when `nan_equal`)."""
+    n = len(c)
+    if n <= 1:
+        return torch.zeros(0, dtype=torch.bool, device=c.device)
+    a = c.gather(torch.arange(0, n - 1, dtype=torch.int64, device=c.device))
+    b = c.gather(torch.arange(1, n, dtype=torch.int64, device=c.device))
+    if c.dtype.is_string:
+        from . import strings as S
+
+        eq = S.compare(a, b, "==")
+    else:
+        eq = a.data == b.data
+        if nan_equal and c.dtype.is_float:
+            eq = eq | (torch.isnan(a.data) & torch.isnan(b.data))
+    ones = torch.ones(n - 1, dtype=torch.bool, device=c.device)
+    av = a.validity if a.validity is not None else ones
+    bv = b.validity if b.validity is not None else ones
+    return (eq & av & bv) | (~av & ~bv)
+
+
 class RecordBatch:
     # _eval_memo: optional CSE scope opened by exprs.eval_scope
     __slots__ = ("names", "columns", "_eval_memo")

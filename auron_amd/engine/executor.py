@@ -22,12 +22,13 @@ import torch
 import torch.distributed as dist
 
 from .. import dtypes, ops
-from ..column import Column, RecordBatch, compact_validity
+from ..column import Column, RecordBatch, adjacent_equal, compact_validity
 from ..dtypes import DataType
 from ..exchange import all_gather_batch, all_to_all
-from ..exprs import AggFunc, Col, WindowFunc
+from ..exprs import AggFunc, Col
 from ..plan import nodes as P
 from ..config import AGG_STREAMING, BROADCAST_CACHE_BYTES, AuronConf
+from .window import exec_window
 
 
 @dataclass
@@ -1160,7 +1161,7 @@ class Executor:
             if n > 1:
                 same = torch.ones(n - 1, dtype=torch.bool, device=device)
                 for i in range(len(knames)):
-                    same &= self._col_eq_adjacent(sc.columns[i])
+                    same &= adjacent_equal(sc.columns[i])
                 first[1:] = ~same
             seg = torch.cumsum(first.to(torch.int64), 0) - 1
             nseg = int(seg[-1].item()) + 1
@@ -2166,595 +2167,4 @@ class Executor:
 
     # --------------------------------------------------------------- window
     def _exec_Window(self, node: P.Window) -> List[RecordBatch]:
-        b = _concat(self.execute(node.child))
-        device = b.device
-        n = b.num_rows
-        if node.partition_by:
-            # partition membership only needs GROUPING, not lexicographic
-            # order: map partition keys (often several strings) to hash
-            # group ids once and sort by the integer id — avoids per-pass
-            # host string-rank sorts that dominated q47/q57/q67
-            pcols = [k.eval(b) for k in node.partition_by]
-            gids0, _ = ops.group_ids(pcols)
-            tmp = RecordBatch(list(b.names) + ["__wgid"],
-                              list(b.columns) + [Column(dtypes.int64, gids0)])
-            skeys = [(Col("__wgid"), True)] + list(node.order_by)
-            perm = self._sort_permutation(tmp, skeys)
-            sb = b.gather(perm)
-            gids = gids0[perm]
-            # normalize arbitrary hash ids to dense segment ids over the
-            # sorted rows
-            if n:
-                changed = torch.zeros(n, dtype=torch.int64, device=device)
-                changed[1:] = (gids[1:] != gids[:-1]).to(torch.int64)
-                seg = torch.cumsum(changed, 0)
-            else:
-                seg = gids
-            nseg = int(seg[-1].item()) + 1 if n else 0
-        else:
-            perm = (self._sort_permutation(b, list(node.order_by))
-                    if node.order_by else
-                    torch.arange(n, dtype=torch.int64, device=device))
-            sb = b.gather(perm)
-            seg = torch.zeros(n, dtype=torch.int64, device=device)
-            nseg = 1 if n else 0
-        seg_start = torch.zeros(max(nseg, 1), dtype=torch.int64, device=device)
-        if n:
-            first_mask = torch.ones(n, dtype=torch.bool, device=device)
-            first_mask[1:] = seg[1:] != seg[:-1]
-            seg_start = torch.nonzero(first_mask, as_tuple=False).flatten()
-        pos_in_seg = torch.arange(n, dtype=torch.int64, device=device) - seg_start[seg] if n else torch.zeros(0, dtype=torch.int64, device=device)
-
-        sb._eval_memo = {}  # CSE scope; sb is operator-local, dies with it
-        names = list(sb.names)
-        cols = list(sb.columns)
-        # RANGE frame with explicit bounds: resolve (a, b) once per node
-        value_frame = None
-        if (node.frame == "range"
-                and not (node.frame_lo is None and node.frame_hi == 0)):
-            value_frame = self._range_frame_bounds(node, sb, seg, seg_start)
-        for al in node.functions:
-            wf: WindowFunc = al.expr  # type: ignore
-            if wf.fn == "row_number":
-                out = Column(dtypes.int64, pos_in_seg + 1)
-            elif wf.fn in ("rank", "dense_rank"):
-                if node.order_by and n:
-                    okeys = [k.eval(sb) for k, _ in node.order_by]
-                    same_as_prev = torch.zeros(n, dtype=torch.bool, device=device)
-                    sp = torch.ones(n - 1, dtype=torch.bool, device=device) if n > 1 else torch.zeros(0, dtype=torch.bool, device=device)
-                    for c in okeys:
-                        eq = self._col_eq_adjacent(c)
-                        sp = sp & eq
-                    same_as_prev[1:] = sp
-                    same_as_prev[seg_start] = False
-                    if wf.fn == "dense_rank":
-                        incr = (~same_as_prev).to(torch.int64)
-                        r = torch.cumsum(incr, 0)
-                        out = Column(dtypes.int64, r - r[seg_start][seg] + 1)
-                    else:
-                        out = Column(dtypes.int64, self._window_rank(
-                            node, sb, seg, seg_start, n, device))
-                else:
-                    out = Column(dtypes.int64, torch.ones(n, dtype=torch.int64, device=device))
-            elif wf.fn in ("sum", "avg", "count", "min", "max"):
-                val = wf.arg.eval(sb)
-                if (val.dtype.code == dtypes.DECIMAL128
-                        or (wf.fn == "sum" and self._sum_needs_128(val.dtype))):
-                    if wf.fn == "sum" and not (node.order_by and n):
-                        # whole-partition sum promoted to decimal128:
-                        # exact limb accumulation (q12/q20/q98 ratios)
-                        if val.dtype.code == dtypes.DECIMAL128:
-                            data, cnt = self._sum128_scatter(seg, max(nseg, 1), val)
-                            out_dt = val.dtype
-                        else:
-                            data, cnt = self._sum_split_128(seg, max(nseg, 1), val)
-                            out_dt = self._state_dtype(
-                                AggFunc("sum", None, name=al.name), val.dtype)
-                        fin = Column(out_dt, data,
-                                     compact_validity(cnt > 0))
-                        out = fin.gather(seg)
-                        names.append(al.name)
-                        cols.append(out)
-                        continue
-                    if (val.dtype.code == dtypes.DECIMAL128
-                            and wf.fn != "count"):
-                        # every other decimal128 frame: exact 128-bit
-                        # prefix / pyramid over the per-row frame (a, b)
-                        out = self._frame_aggregate_i128(
-                            wf.fn, val, *self._window_frame_bounds(
-                                node, sb, seg, seg_start, value_frame))
-                        self.ctx.metrics["window.frame_i128_rows"] = \
-                            self.ctx.metrics.get(
-                                "window.frame_i128_rows", 0) + n
-                        names.append(al.name)
-                        cols.append(out)
-                        continue
-                    # decimal64 sums wide enough to need 128 bits (and
-                    # count over decimal128): float64 accumulator
-                    from ..exprs import _cast_col
-
-                    val = _cast_col(val, dtypes.float64)
-                bounded = (node.frame == "rows"
-                           and not (node.frame_lo is None
-                                    and node.frame_hi == 0))
-                if value_frame is not None:
-                    out = self._frame_aggregate(wf.fn, val, *value_frame)
-                elif bounded and n:
-                    out = self._bounded_rows_window(
-                        wf.fn, val, seg, seg_start,
-                        node.frame_lo, node.frame_hi)
-                elif node.order_by and n:
-                    # Spark's default frame with ORDER BY: unbounded
-                    # preceding .. current row (running aggregate)
-                    out = self._running_window(wf.fn, val, seg, seg_start)
-                    if node.frame == "range":
-                        # RANGE frame: peer rows (equal order keys within the
-                        # partition) share the value at the LAST peer row
-                        out = out.gather(self._peer_end(node, sb, seg_start, n,
-                                                        device))
-                else:
-                    acc, cnt = ops.agg_scatter(seg, max(nseg, 1), val, wf.fn if wf.fn != "count" else "count")
-                    fin = self._finalize_agg(AggFunc(wf.fn, None, name=al.name), val.dtype, acc, cnt)
-                    out = fin.gather(seg)
-            elif wf.fn in ("lead", "lag"):
-                val = wf.arg.eval(sb)
-                k = wf.offset if wf.offset else 1
-                shift = -k if wf.fn == "lead" else k
-                idx = torch.arange(n, dtype=torch.int64, device=device) - shift
-                ok = (idx >= 0) & (idx < n)
-                idx_c = idx.clamp(0, max(n - 1, 0))
-                ok = ok & (seg[idx_c] == seg) if n else ok
-                gi = torch.where(ok, idx_c, torch.full_like(idx_c, -1))
-                out = val.gather(gi, may_have_negative=True)
-                if wf.default is not None and out.validity is not None:
-                    from ..exprs import Literal, eval_scope
-
-                    dcol = Literal(wf.default, val.dtype).eval(sb)
-                    miss = ~out.validity
-                    # only frame-escapes get the default; genuine nulls stay
-                    src_valid = val.validity if val.validity is not None else None
-                    if src_valid is not None:
-                        esc = miss & ~torch.where(gi >= 0, ~src_valid[gi.clamp(min=0)],
-                                                  torch.zeros_like(miss))
-                    else:
-                        esc = miss
-                    data = torch.where(esc, dcol.data, out.data)
-                    validity = compact_validity(out.validity | esc)
-                    out = Column(out.dtype, data, validity)
-            elif wf.fn in ("percent_rank", "cume_dist", "ntile"):
-                seg_last = (torch.cat([seg_start[1:] - 1,
-                                       torch.tensor([n - 1], dtype=torch.int64,
-                                                    device=device)])
-                            if n else seg_start)
-                seg_len = seg_last[seg] - seg_start[seg] + 1 if n else seg
-                if wf.fn == "percent_rank":
-                    rank = self._window_rank(node, sb, seg, seg_start, n, device)
-                    denom = (seg_len - 1).clamp(min=1).to(torch.float64)
-                    out = Column(dtypes.float64,
-                                 (rank - 1).to(torch.float64) / denom)
-                elif wf.fn == "cume_dist":
-                    pend = self._peer_end(node, sb, seg_start, n, device)
-                    out = Column(dtypes.float64,
-                                 (pend - seg_start[seg] + 1).to(torch.float64)
-                                 / seg_len.to(torch.float64))
-                else:  # ntile(k): first (len%k) buckets get one extra row
-                    k = wf.offset if wf.offset else 1
-                    base = torch.div(seg_len, k, rounding_mode="floor")
-                    rem = seg_len - base * k
-                    cut = rem * (base + 1)
-                    lo = torch.div(pos_in_seg, (base + 1).clamp(min=1),
-                                   rounding_mode="floor") + 1
-                    hi = rem + torch.div((pos_in_seg - cut), base.clamp(min=1),
-                                         rounding_mode="floor") + 1
-                    out = Column(dtypes.int64,
-                                 torch.where(pos_in_seg < cut, lo, hi))
-            elif wf.fn in ("first_value", "last_value", "nth_value"):
-                val = wf.arg.eval(sb)
-                if value_frame is not None and wf.fn != "nth_value":
-                    fa, fb, fempty = value_frame
-                    at = fa if wf.fn == "first_value" else fb
-                    out = val.gather(
-                        torch.where(fempty, torch.full_like(at, -1), at),
-                        may_have_negative=True)
-                elif wf.fn == "first_value":
-                    out = val.gather(seg_start[seg]) if n else val
-                elif wf.fn == "last_value":
-                    # frame unbounded preceding..current: ROWS -> current row;
-                    # RANGE -> last peer row
-                    if node.frame == "range" and node.order_by and n:
-                        out = val.gather(self._peer_end(node, sb, seg_start, n,
-                                                        device))
-                    else:
-                        out = val
-                else:
-                    k = wf.offset if wf.offset else 1
-                    tgt = seg_start[seg] + (k - 1) if n else seg
-                    ok = pos_in_seg >= (k - 1)
-                    out = val.gather(torch.where(ok, tgt, torch.full_like(tgt, -1)),
-                                     may_have_negative=True)
-            else:
-                raise NotImplementedError(f"window fn {wf.fn}")
-            names.append(al.name)
-            cols.append(out)
-        return [RecordBatch(names, cols)]
-
-    def _window_rank(self, node, sb, seg, seg_start, n, device):
-        """SQL rank(): 1 + index distance from the last order-key change."""
-        if not (node.order_by and n):
-            return torch.ones(n, dtype=torch.int64, device=device)
-        okeys = [k.eval(sb) for k, _ in node.order_by]
-        same_as_prev = torch.zeros(n, dtype=torch.bool, device=device)
-        if n > 1:
-            sp = torch.ones(n - 1, dtype=torch.bool, device=device)
-            for c in okeys:
-                sp = sp & self._col_eq_adjacent(c)
-            same_as_prev[1:] = sp
-        same_as_prev[seg_start] = False
-        gpos = torch.arange(n, dtype=torch.int64, device=device)
-        change_pos = torch.where(same_as_prev, torch.full_like(gpos, -1), gpos)
-        lcp = torch.cummax(change_pos, 0).values
-        return lcp - seg_start[seg] + 1
-
-    def _peer_end(self, node, sb, seg_start, n, device):
-        """Per row: index of its last peer (equal order keys in partition)."""
-        peer_first = torch.ones(n, dtype=torch.bool, device=device)
-        if node.order_by and n > 1:
-            sp = torch.ones(n - 1, dtype=torch.bool, device=device)
-            for k, _ in node.order_by:
-                sp = sp & self._col_eq_adjacent(k.eval(sb))
-            peer_first[1:] = ~sp
-        peer_first[seg_start] = True
-        pg = torch.cumsum(peer_first.to(torch.int64), 0) - 1
-        pstart = torch.nonzero(peer_first, as_tuple=False).flatten()
-        pend = torch.cat([pstart[1:] - 1,
-                          torch.tensor([n - 1], dtype=torch.int64, device=device)])
-        return pend[pg]
-
-    def _range_frame_bounds(self, node, sb, seg, seg_start):
-        """RANGE BETWEEN <lo> AND <hi> with explicit bounds (Spark's
-        semantics) -> per-row inclusive frame (a, b, empty) over the sorted
-        rows, or None for an empty input.
-
-        CURRENT ROW is the whole peer group; a value offset compares the
-        single ORDER BY key (k+lo <= key <= k+hi ascending, k-lo >= key >=
-        k-hi descending; integer k±offset saturates). Rows whose key is
-        NULL — or NaN for float keys — are special: their offset/current
-        bounds resolve to their own peer group, and an ordinary row's offset
-        bound never reaches them. Unbounded is the partition edge."""
-        lo, hi = node.frame_lo, node.frame_hi
-        by_value = ((lo is not None and lo != 0) or (hi != "U" and hi != 0))
-        key = None
-        if by_value:
-            if len(node.order_by) != 1:
-                raise ValueError(
-                    "a RANGE frame with a value offset needs exactly one "
-                    f"ORDER BY key, got {len(node.order_by)}")
-            key = node.order_by[0][0].eval(sb)
-            kdt = key.dtype
-            if not (kdt.is_integer or kdt.is_float or kdt.code in (
-                    dtypes.DATE32, dtypes.TIMESTAMP, dtypes.DECIMAL64)):
-                raise NotImplementedError(
-                    f"RANGE frame value offsets over a {kdt.name} key")
-            want = float if kdt.is_float else int
-            for v in (lo, hi):
-                if v is not None and v != "U" and (
-                        isinstance(v, bool) or not isinstance(v, (int, float))
-                        or (want is int and not isinstance(v, int))):
-                    raise ValueError(
-                        f"RANGE frame bound {v!r} does not fit a {kdt.name} "
-                        "key")
-        n = seg.numel()
-        if n == 0:
-            return None
-        device = seg.device
-        idx = torch.arange(n, dtype=torch.int64, device=device)
-        first = seg_start[seg]
-        seg_last = torch.cat([seg_start[1:] - 1,
-                              torch.tensor([n - 1], dtype=torch.int64,
-                                           device=device)])
-        last = seg_last[seg]
-        # peer groups (NaN keys are peers of each other, as NULLs are)
-        peer_first = torch.zeros(n, dtype=torch.bool, device=device)
-        if node.order_by and n > 1:
-            sp = torch.ones(n - 1, dtype=torch.bool, device=device)
-            for k, _ in node.order_by:
-                sp = sp & self._col_eq_adjacent(k.eval(sb), nan_equal=True)
-            peer_first[1:] = ~sp
-        peer_first[seg_start] = True
-        pstart = torch.nonzero(peer_first, as_tuple=False).flatten()
-        pend = torch.cat([pstart[1:] - 1,
-                          torch.tensor([n - 1], dtype=torch.int64,
-                                       device=device)])
-        pg = torch.cumsum(peer_first.to(torch.int64), 0) - 1
-        a, b = pstart[pg], pend[pg]
-        if by_value:
-            asc = node.order_by[0][1]
-            if key.dtype.is_float:
-                kd = key.data.to(torch.float64)
-                special = torch.isnan(kd)
-            else:
-                kd = key.data.to(torch.int64)
-                special = torch.zeros(n, dtype=torch.bool, device=device)
-            if key.validity is not None:
-                special = special | ~key.validity
-            # ordinary keys sit contiguously inside each partition (NULLs
-            # and NaNs sort to its ends): per-partition window [slo, shi]
-            ordinary = ~special
-            nseg = seg_start.numel()
-            slo = torch.full((nseg,), n, dtype=torch.int64, device=device)
-            shi = torch.full((nseg,), -1, dtype=torch.int64, device=device)
-            slo.scatter_reduce_(0, seg[ordinary], idx[ordinary], "amin")
-            shi.scatter_reduce_(0, seg[ordinary], idx[ordinary], "amax")
-            # (a partition without ordinary keys keeps the empty [n, -1])
-            ka, kb = ops.window_range_bounds(kd, slo[seg], shi[seg], lo, hi,
-                                             descending=not asc)
-            a = torch.where(special, a, ka)
-            b = torch.where(special, b, kb)
-            self.ctx.metrics["window.range_frame_rows"] = \
-                self.ctx.metrics.get("window.range_frame_rows", 0) + n
-        if lo is None:
-            a = first
-        if hi == "U":
-            b = last
-        return a, b, a > b
-
-    def _window_frame_bounds(self, node, sb, seg, seg_start, value_frame):
-        """The Window node's frame as per-row inclusive (a, b, empty) over
-        the sorted rows, whatever its kind: an explicit RANGE frame
-        (`value_frame`, already resolved), bounded ROWS, the default running
-        frame (ROWS: up to the current row, RANGE: up to its last peer), or
-        the whole partition without ORDER BY."""
-        if value_frame is not None:
-            return value_frame
-        n = seg.numel()
-        device = seg.device
-        if n == 0:
-            z = torch.zeros(0, dtype=torch.int64, device=device)
-            return z, z, z > z
-        if node.frame == "rows" and not (node.frame_lo is None
-                                         and node.frame_hi == 0):
-            return self._rows_frame_bounds(
-                *self._partition_edges(seg, seg_start), node.frame_lo,
-                node.frame_hi)
-        a, b = self._partition_edges(seg, seg_start)
-        if node.order_by:
-            if node.frame == "range":
-                b = self._peer_end(node, sb, seg_start, n, device)
-            else:
-                b = torch.arange(n, dtype=torch.int64, device=device)
-        return a, b, a > b
-
-    @staticmethod
-    def _partition_edges(seg, seg_start):
-        """Per row: index of its partition's first and last row."""
-        n = seg.numel()
-        counts = torch.bincount(seg, minlength=int(seg.max().item()) + 1 if n else 1)
-        first = seg_start[seg]
-        return first, first + counts[seg] - 1
-
-    @staticmethod
-    def _rows_frame_bounds(first, last, lo, hi):
-        """ROWS BETWEEN lo AND hi (row offsets; None / "U" unbounded) ->
-        (a, b, empty), clamped to the row's partition [first, last]."""
-        i = torch.arange(first.numel(), dtype=torch.int64,
-                         device=first.device)
-        a = first if lo is None else torch.maximum(i + int(lo), first)
-        b = last if hi == "U" else torch.minimum(i + int(hi), last)
-        return a, b, a > b
-
-    @staticmethod
-    def _prefix_range(P, a, b, empty):
-        """P[b] - (a > 0 ? P[a-1] : 0) of an inclusive prefix array, zero
-        for an empty frame."""
-        hi_v = P[b.clamp(min=0)]
-        lo_i = a - 1
-        lo_v = torch.where(lo_i >= 0, P[lo_i.clamp(min=0)],
-                           torch.zeros((), dtype=P.dtype, device=P.device))
-        out = hi_v - lo_v
-        return torch.where(empty, torch.zeros_like(out), out)
-
-    def _frame_aggregate_i128(self, fn: str, val: Column, a: torch.Tensor,
-                              b: torch.Tensor, empty: torch.Tensor) -> Column:
-        """sum/avg/min/max of a DECIMAL128 column over per-row inclusive
-        frames [a, b], exact: sums are differences of one unsegmented
-        128-bit prefix sum (wrapped prefixes cancel), min/max come from the
-        128-bit frame primitive. Nulls are skipped; a frame with no valid
-        value gives NULL. sum/min/max keep the argument's type, avg is
-        float64."""
-        assert val.dtype.code == dtypes.DECIMAL128, val.dtype
-        device = a.device
-        valid = val.validity
-        if valid is None:
-            cnt = torch.where(empty, torch.zeros_like(a), b - a + 1)
-        else:
-            cnt = self._prefix_range(torch.cumsum(valid.to(torch.int64), 0),
-                                     a, b, empty)
-        validity = compact_validity(cnt > 0)
-        if fn in ("sum", "avg"):
-            s = ops.window_frame_sum_i128(
-                ops.prefix_sum_i128(val.data, valid), a, b)
-            if fn == "sum":
-                return Column(val.dtype, s, validity)
-            from ..exprs import dec128_to_float64
-
-            data = dec128_to_float64(s, val.dtype.scale) \
-                / cnt.clamp(min=1).to(torch.float64)
-            return Column(dtypes.float64, data, validity)
-        assert fn in ("min", "max"), fn
-        x = val.data
-        if valid is not None:
-            ident = torch.tensor(
-                ops._I128_MAX if fn == "min" else ops._I128_MIN,
-                dtype=torch.int64, device=device)
-            x = torch.where(valid.unsqueeze(1), x, ident)
-        # an empty frame (a > b) yields the identity; cnt == 0 makes it NULL
-        m = ops.window_frame_minmax_i128(x, a, b, fn)
-        return Column(val.dtype, m, validity)
-
-    def _frame_aggregate(self, fn: str, val: Column, a: torch.Tensor,
-                         b: torch.Tensor, empty: torch.Tensor) -> Column:
-        """sum/avg/count/min/max over per-row inclusive frames [a, b]
-        (`empty` marks a > b): prefix-sum differences for sum/avg/count,
-        the frame min/max primitive for min/max. Nulls are skipped; a
-        frame with no valid value gives NULL (count 0)."""
-        device = a.device
-        n = a.numel()
-        valid = val.validity if val.validity is not None else \
-            torch.ones(n, dtype=torch.bool, device=device)
-        C = torch.cumsum(valid.to(torch.int64), 0)
-
-        def rng(P):
-            return self._prefix_range(P, a, b, empty)
-
-        cnt = rng(C)
-        if fn == "count":
-            return Column(dtypes.int64, cnt)
-        if fn in ("sum", "avg"):
-            vd = val.data
-            if vd.dtype not in (torch.float64, torch.float32):
-                vd = vd.to(torch.int64)
-            x = torch.where(valid, vd, torch.zeros_like(vd))
-            s = rng(torch.cumsum(x, 0))
-            if fn == "avg":
-                data = s.to(torch.float64) / cnt.clamp(min=1).to(torch.float64)
-                if val.dtype.code == dtypes.DECIMAL64:
-                    data = data / (10.0 ** val.dtype.scale)
-                return Column(dtypes.float64, data,
-                              compact_validity(cnt > 0))
-            out_dt = val.dtype if val.dtype.code == dtypes.DECIMAL64 else (
-                dtypes.float64 if val.dtype.is_float else dtypes.int64)
-            return Column(out_dt, s.to(out_dt.torch_dtype),
-                          compact_validity(cnt > 0))
-        assert fn in ("min", "max"), fn
-        vd = val.data
-        work = vd.to(torch.float64) if vd.dtype.is_floating_point \
-            else vd.to(torch.int64)
-        if work.dtype == torch.int64:
-            fill = torch.iinfo(torch.int64).max if fn == "min" \
-                else torch.iinfo(torch.int64).min
-        else:
-            fill = float("inf") if fn == "min" else float("-inf")
-        x = torch.where(valid, work, torch.full_like(work, fill))
-        # an empty frame (a > b) yields the identity; cnt == 0 makes it NULL
-        m = ops.window_frame_minmax(x, a, b, fn)
-        self.ctx.metrics["window.frame_minmax_rows"] = \
-            self.ctx.metrics.get("window.frame_minmax_rows", 0) + n
-        return Column(val.dtype, m.to(vd.dtype), compact_validity(cnt > 0))
-
-    def _bounded_rows_window(self, fn: str, val: Column, seg: torch.Tensor,
-                             seg_start: torch.Tensor, lo, hi) -> Column:
-        """Explicit ROWS BETWEEN bounds (window_exec.rs frame processors):
-        sum/avg/count via segment-clamped prefix sums; min/max via a
-        shifted-compare chain over a short bounded span, else via the
-        frame min/max primitive (unbounded side or span >= 1024)."""
-        device = seg.device
-        n = seg.numel()
-        first, last = self._partition_edges(seg, seg_start)
-        a, b, empty = self._rows_frame_bounds(first, last, lo, hi)
-        i = torch.arange(n, dtype=torch.int64, device=device)
-        valid = val.validity if val.validity is not None else \
-            torch.ones(n, dtype=torch.bool, device=device)
-        if fn in ("sum", "avg", "count"):
-            return self._frame_aggregate(fn, val, a, b, empty)
-        if not (isinstance(lo, int) and isinstance(hi, int)
-                and hi - lo < 1024):
-            return self._frame_aggregate(fn, val, a, b, empty)
-        # min/max: chain of shifted comparisons over the span
-        cmp = torch.minimum if fn == "min" else torch.maximum
-        acc = None
-        acc_ok = torch.zeros(n, dtype=torch.bool, device=device)
-        for off in range(lo, hi + 1):
-            j = (i + off).clamp(0, max(n - 1, 0))
-            ok = (i + off >= first) & (i + off <= last) & valid[j]
-            v = val.data[j]
-            if acc is None:
-                acc = v.clone()
-                acc_ok = ok.clone()
-            else:
-                take_new = ok & (~acc_ok)
-                both = ok & acc_ok
-                acc = torch.where(take_new, v, acc)
-                acc = torch.where(both, cmp(acc, v), acc)
-                acc_ok = acc_ok | ok
-        return Column(val.dtype, acc, compact_validity(acc_ok))
-
-    def _running_window(self, fn: str, val: Column, seg: torch.Tensor,
-                        seg_start: torch.Tensor) -> Column:
-        """Cumulative frame within segments (nulls skipped)."""
-        device = seg.device
-        n = seg.numel()
-        v = val.data
-        if v.dtype in (torch.int8, torch.int16, torch.int32):
-            v = v.to(torch.int64)
-        elif v.dtype == torch.float32:
-            v = v.to(torch.float64)
-        valid = val.validity if val.validity is not None else torch.ones(n, dtype=torch.bool, device=device)
-        cum_valid = torch.cumsum(valid.to(torch.int64), 0)
-        base_valid = cum_valid[seg_start][seg] - valid[seg_start][seg].to(torch.int64)
-        run_count = cum_valid - base_valid
-        if fn == "count":
-            return Column(dtypes.int64, run_count)
-        if fn in ("sum", "avg"):
-            z = torch.where(valid, v, torch.zeros_like(v))
-            cs = torch.cumsum(z, 0)
-            base = cs[seg_start][seg] - z[seg_start][seg]
-            run = cs - base
-            validity = compact_validity(run_count > 0)
-            if fn == "avg":
-                return Column(dtypes.float64,
-                              run.to(torch.float64) / run_count.clamp(min=1).to(torch.float64),
-                              validity)
-            dt = dtypes.float64 if run.dtype == torch.float64 else dtypes.int64
-            if val.dtype.code == dtypes.DECIMAL64:
-                dt = val.dtype
-            return Column(dt, run, validity)
-        # running min/max: exact segmented scan in the VALUE domain (int64
-        # for int/decimal, float64 for floats) via log2(maxseglen) doubling
-        # steps — never routed through shifted floats, so int64/decimal
-        # values beyond 2^53 stay exact (advisor finding r1).
-        is_int = v.dtype == torch.int64
-        work = v if is_int else v.to(torch.float64)
-        if fn == "min":
-            fill = torch.iinfo(torch.int64).max if is_int else float("inf")
-            combine = torch.minimum
-        else:
-            fill = torch.iinfo(torch.int64).min if is_int else float("-inf")
-            combine = torch.maximum
-        run = torch.where(valid, work, torch.full_like(work, fill))
-        start = seg_start[seg]
-        pos = torch.arange(n, dtype=torch.int64, device=device)
-        maxlen = int((seg_start[1:] - seg_start[:-1]).max().item()) if seg_start.numel() > 1 else n
-        maxlen = max(maxlen, n - int(seg_start[-1].item()) if seg_start.numel() else n)
-        off = 1
-        while off < maxlen:
-            cand = torch.empty_like(run)
-            cand[off:] = run[:-off]
-            ok = (pos - off) >= start
-            run = torch.where(ok, combine(run, cand), run)
-            off <<= 1
-        validity = compact_validity(run_count > 0)
-        if val.dtype.code == dtypes.DECIMAL64:
-            return Column(val.dtype, run, validity)
-        if val.dtype.is_integer:
-            return Column(dtypes.int64, run, validity)
-        return Column(dtypes.float64, run, validity)
-
-    def _col_eq_adjacent(self, c: Column, nan_equal: bool = False) -> torch.Tensor:
-        """eq mask between row i and i-1, for rows 1..n-1 (null==null;
-        NaN==NaN only when `nan_equal`)."""
-        n = len(c)
-        if n <= 1:
-            return torch.zeros(0, dtype=torch.bool, device=c.device)
-        a = c.gather(torch.arange(0, n - 1, dtype=torch.int64, device=c.device))
-        bcol = c.gather(torch.arange(1, n, dtype=torch.int64, device=c.device))
-        if c.dtype.is_string:
-            from .. import strings as S
-
-            eq = S.compare(a, bcol, "==")
-        else:
-            eq = a.data == bcol.data
-            if nan_equal and c.dtype.is_float:
-                eq = eq | (torch.isnan(a.data) & torch.isnan(bcol.data))
-        av = a.validity if a.validity is not None else torch.ones(n - 1, dtype=torch.bool, device=c.device)
-        bv = bcol.validity if bcol.validity is not None else torch.ones(n - 1, dtype=torch.bool, device=c.device)
-        return (eq & av & bv) | (~av & ~bv)
+        return exec_window(self, node, _concat(self.execute(node.child)))

@@ -11,6 +11,7 @@ from test_window_range_frames import (BOUNDS, FUNCS, INT64_MAX, INT64_MIN,
                                       make_rows, minmax_values, raw,
                                       run_sql, run_window, same, scaled,
                                       sorted_key_case)
+from test_window_functions import all_funcs, by_rid, window
 
 pytestmark = pytest.mark.gpu
 
@@ -110,3 +111,23 @@ def test_desc_float_range_frame_on_device_matches_cpu():
         for r in want:
             assert all(same(g, w) for g, w in zip(got[r], want[r])), \
                 (lo, hi, r, got[r], want[r])
+
+
+def test_all_functions_in_one_node_on_device_match_cpu():
+    """Every window function in one node, so that they share the node's
+    partitions, peer groups and frame: the default RANGE frame and a
+    bounded ROWS frame."""
+    native.require()
+    rows = make_rows("int64", 300, 7, seed=3307)
+    fns = all_funcs(300)
+    for frame, lo, hi in (("range", None, 0), ("rows", -2, 1)):
+        out, _ = window(rows, fns, frame, lo, hi, device=DEV)
+        cpu, _ = window(rows, fns, frame, lo, hi)
+        assert out.names == cpu.names
+        assert all(c.data.device.type == "cuda" for c in out.columns)
+        for name, _ in fns:
+            got, want = by_rid(out, name), by_rid(cpu, name)
+            assert got.keys() == want.keys()
+            for r in want:
+                assert same(got[r], want[r]), \
+                    (frame, name, r, got[r], want[r])
