@@ -118,12 +118,14 @@ HBM_CACHE_RESERVE = _opt("spark.auron.scan.hbmStagedCache.reserveFraction",
                          "never consume (evicts itself under pressure)")
 SCAN_DELTA_NATIVE = _opt("spark.auron.scan.deltaNative.enable", True, bool,
                          "decode DELTA_BINARY_PACKED pages and "
-                         "DELTA_LENGTH_BYTE_ARRAY string pages with the "
-                         "k_pq_delta_* kernels from a host-built miniblock "
-                         "index (off: DELTA_BINARY_PACKED is expanded to "
-                         "PLAIN by one host job per page and "
-                         "DELTA_LENGTH_BYTE_ARRAY columns take the pyarrow "
-                         "host read)",
+                         "DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY string "
+                         "pages with the k_pq_delta_* kernels from a "
+                         "host-built miniblock index, DELTA_BYTE_ARRAY "
+                         "strings rebuilt by k_pq_dba_bytes (off: "
+                         "DELTA_BINARY_PACKED is expanded to PLAIN by one "
+                         "host job per page and DELTA_LENGTH_BYTE_ARRAY and "
+                         "DELTA_BYTE_ARRAY columns take the pyarrow host "
+                         "read)",
                          env="AURON_SCAN_DELTA_NATIVE")
 SCAN_PREFETCH = _opt("spark.auron.scan.streamPrefetch", 2, int,
                      "files decoded ahead of the consumer on the "

@@ -79,6 +79,12 @@ def _try_load():
     lib.au_pq_delta_emit.argtypes = [c, i64, c, i64, c, c, c, ctypes.c_int, c]
     for f in ("au_pq_delta_sums", "au_pq_delta_scan", "au_pq_delta_emit"):
         getattr(lib, f).restype = ctypes.c_int
+    lib.au_host_dba_decode.argtypes = [c, i64, c, c, c, c, i64, c, i64]
+    lib.au_host_dba_decode.restype = i64
+    lib.au_pq_dba_tile.argtypes = []
+    lib.au_pq_dba_tile.restype = i64
+    lib.au_pq_dba_bytes.argtypes = [c, c, c, c, i64, i64, c, c, c]
+    lib.au_pq_dba_bytes.restype = ctypes.c_int
     lib.au_pq_rle_idx.argtypes = [c, ctypes.c_int, c, c, c, c]
     lib.au_pq_scatter.argtypes = [c, ctypes.c_int, c, c, c, c, ctypes.c_int, i64, c]
     lib.au_pq_copy_plain.argtypes = [c, ctypes.c_int, c, c, ctypes.c_int, i64, c]

@@ -11,6 +11,9 @@
 //                    vectorized copy
 //  - k_pq_delta_*:   DELTA_BINARY_PACKED values and DELTA_LENGTH_BYTE_ARRAY
 //                    lengths, one wave per miniblock (host-indexed headers)
+//  - k_pq_dba_bytes: DELTA_BYTE_ARRAY strings rebuilt from the prefix and
+//                    suffix lengths the delta kernels decoded, one wave
+//                    per segment of values, seeded from source bytes only
 //
 // Page descriptor layout (int64 x 6, packed by parquet_native.py):
 //   [0]=def_off [1]=def_len [2]=values_off [3]=n_values [4]=row_start [5]=pad
@@ -821,5 +824,173 @@ AU_EXPORT int au_pq_delta_emit(const void* mb_dev, int64_t nmb,
                        (const DlMini*)mb_dev, nmb, (const DlPage*)pg_dev,
                        npages, (const uint8_t*)buf, (const uint64_t*)excl,
                        (uint64_t*)out);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------- DELTA_BYTE_ARRAY
+// Parquet encoding 7: a page is two DELTA_BINARY_PACKED streams (prefix
+// lengths, suffix lengths) and the suffix bytes. String i is the first
+// P[i] bytes of string i-1 followed by suffix i. The lengths come from the
+// k_pq_delta_* kernels; what is left is the byte reconstruction, which
+// looks serial because every string leans on the one before.
+//
+// Serial host reference, bounds-checked: the oracle for k_pq_dba_bytes
+// and the CPU read path. P/S = prefix/suffix lengths, so = absolute
+// offset of each suffix in buf, O = output offset of each string.
+// Returns 0, or -1 when an entry points outside buf/out or a prefix is
+// longer than the string before.
+AU_EXPORT int64_t au_host_dba_decode(const uint8_t* buf, int64_t buf_len,
+                                     const int64_t* P, const int64_t* S,
+                                     const int64_t* so, const int64_t* O,
+                                     int64_t n, uint8_t* out,
+                                     int64_t out_len) {
+  int64_t prev_o = 0, prev_l = 0;
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t p = P[i], s = S[i], o = O[i], src = so[i];
+    if (p < 0 || s < 0 || p > prev_l) return -1;
+    if (o < 0 || o > out_len || p > out_len - o || s > out_len - o - p)
+      return -1;
+    if (src < 0 || src > buf_len || s > buf_len - src) return -1;
+    for (int64_t j = 0; j < p; j++) out[o + j] = out[prev_o + j];
+    for (int64_t j = 0; j < s; j++) out[o + p + j] = buf[src + j];
+    prev_o = o;
+    prev_l = p + s;
+  }
+  return 0;
+}
+
+// Device reconstruction without any store->load dependency through
+// memory. One wave owns a segment of `seg` consecutive values of the
+// chunk's compact stream (pages are nothing special: so[] is absolute)
+// and keeps the "current string" position-striped in registers: lane l
+// holds byte positions t0 + l + 64*r of the tile [t0, t0 + DBA_TILE).
+// For string i, positions P[i] <= j < L[i] are loaded from suffix i and
+// overwrite the tile, positions j < L[i] are stored to out[O[i] + j], and
+// positions j < P[i] are simply what the string before left there. A lane
+// only ever touches its own positions: no barrier, no cross-lane bytes.
+//
+// Seed: before its first string s0 the tile must hold positions
+// j < P[s0] of string s0-1. Walking back k = s0-1, s0-2, ... with
+// need = min(P[s0], t0 + DBA_TILE): whenever P[k] < need, positions
+// [max(P[k], t0), need) are bytes of suffix k, and need = P[k]; done when
+// need <= t0. The walk takes 64 P[k] per step (running minimum by wave
+// scan) and reads source bytes only, never another wave's output.
+// P[0] == 0 ends every walk at the latest.
+//
+// Strings longer than the tile repeat seed and forward pass per tile;
+// strings that end before t0 contribute nothing to that tile (the next
+// string's prefix cannot reach into it either).
+//
+// The kernel trusts its inputs like k_pq_delta_emit: the caller has
+// checked P, S >= 0, P[0] == 0, P[i] <= L[i-1], and that every suffix
+// lies inside its page. Metadata loads in the forward pass are
+// wave-uniform; all stores are per-lane byte stores.
+#define DBA_TILE 256
+#define DBA_REGS (DBA_TILE / 64)
+
+__device__ __forceinline__ int64_t dba_lane64(int64_t v, int lane) {
+  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)(uint64_t)v, lane);
+  const uint32_t hi =
+      __builtin_amdgcn_readlane((uint32_t)((uint64_t)v >> 32), lane);
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+__global__ void __launch_bounds__(256)
+k_pq_dba_bytes(const int64_t* __restrict__ P, const int64_t* __restrict__ S,
+               const int64_t* __restrict__ so, const int64_t* __restrict__ O,
+               int64_t n, int64_t seg, const uint8_t* __restrict__ buf,
+               uint8_t* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 +
+                       __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  const int64_t nseg = (n + seg - 1) / seg;
+  for (int64_t g = wave; g < nseg; g += nwaves) {  // wave-uniform
+    const int64_t s0 = g * seg;
+    const int64_t s1 = s0 + seg < n ? s0 + seg : n;
+    // longest string of the segment: how many tiles it takes
+    int64_t maxl = 0;
+    for (int64_t i = s0 + lane; i < s1; i += 64) {
+      const int64_t l = P[i] + S[i];
+      maxl = l > maxl ? l : maxl;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      const int64_t t = __shfl_xor((long long)maxl, off, 64);
+      maxl = t > maxl ? t : maxl;
+    }
+    maxl = dba_lane64(maxl, 0);
+    const int64_t p0 = P[s0];
+    for (int64_t t0 = 0; t0 < maxl; t0 += DBA_TILE) {
+      uint8_t tile[DBA_REGS];
+#pragma unroll
+      for (int r = 0; r < DBA_REGS; r++) tile[r] = 0;
+
+      // ---- seed: positions [t0, need) of string s0-1
+      int64_t need = p0 < t0 + DBA_TILE ? p0 : t0 + DBA_TILE;
+      for (int64_t kb = s0 - 1; need > t0; kb -= 64) {
+        const int64_t k = kb - lane;
+        const int64_t pk = k >= 0 ? P[k] : 0;
+        // inclusive running minimum over need, P[kb], P[kb-1], ...
+        int64_t incl = pk < need ? pk : need;
+        for (int d = 1; d < 64; d <<= 1) {
+          const int64_t t = __shfl_up((long long)incl, d, 64);
+          if (lane >= d && t < incl) incl = t;
+        }
+        int64_t before = __shfl_up((long long)incl, 1, 64);
+        if (lane == 0) before = need;
+        // strings whose suffix supplies positions [max(pk, t0), before)
+        unsigned long long m = __ballot(pk < before && before > t0);
+        while (m) {  // wave-uniform
+          const int b = __ffsll(m) - 1;
+          m &= m - 1;
+          const int64_t pb = dba_lane64(pk, b);
+          const int64_t hi = dba_lane64(before, b);
+          const int64_t lo = pb > t0 ? pb : t0;
+          const uint8_t* src = buf + (so[kb - b] - pb);
+#pragma unroll
+          for (int r = 0; r < DBA_REGS; r++) {
+            const int64_t j = t0 + lane + 64 * r;
+            if (j >= lo && j < hi) tile[r] = src[j];
+          }
+        }
+        need = dba_lane64(incl, 63);
+      }
+
+      // ---- forward pass over the segment's strings
+      for (int64_t i = s0; i < s1; i++) {
+        const int64_t p = P[i];
+        const int64_t l = p + S[i];
+        if (l <= t0) continue;
+        const uint8_t* src = buf + (so[i] - p);
+        uint8_t* dst = out + O[i];
+#pragma unroll
+        for (int r = 0; r < DBA_REGS; r++) {
+          if (t0 + 64 * r >= l) break;  // wave-uniform
+          const int64_t j = t0 + lane + 64 * r;
+          if (j >= p && j < l) tile[r] = src[j];
+          if (j < l) dst[j] = tile[r];
+        }
+      }
+    }
+  }
+}
+
+AU_EXPORT int64_t au_pq_dba_tile() { return DBA_TILE; }
+
+// P, S, so, O: int64[n] device arrays of the chunk's compact stream;
+// `seg` values per wave; out holds sum(P + S) bytes.
+AU_EXPORT int au_pq_dba_bytes(const void* P, const void* S, const void* so,
+                              const void* O, int64_t n, int64_t seg,
+                              const void* buf, void* out, void* stream) {
+  if (n <= 0) return 0;
+  if (seg <= 0) return (int)hipErrorInvalidValue;
+  const int64_t nseg = (n + seg - 1) / seg;
+  int64_t g = (nseg + 3) / 4;
+  if (g > 2048) g = 2048;
+  hipLaunchKernelGGL(k_pq_dba_bytes, dim3((uint32_t)g), dim3(256), 0,
+                     (hipStream_t)stream, (const int64_t*)P,
+                     (const int64_t*)S, (const int64_t*)so,
+                     (const int64_t*)O, n, seg, (const uint8_t*)buf,
+                     (uint8_t*)out);
   return (int)hipGetLastError();
 }

@@ -17,11 +17,13 @@ INT32/INT64 (the host indexes the block/miniblock headers once per file,
 the k_pq_delta_* kernels unpack and prefix-sum the values, one wave per
 miniblock); BYTE_ARRAY strings dictionary-encoded (dictionary page
 parsed host-side, per-row bytes gathered on device), PLAIN (host offset
-walk, device byte gather) and DELTA_LENGTH_BYTE_ARRAY (lengths decoded by
-the same delta kernels, device byte gather). With
+walk, device byte gather), DELTA_LENGTH_BYTE_ARRAY (lengths decoded by
+the same delta kernels, device byte gather) and DELTA_BYTE_ARRAY (prefix
+and suffix lengths decoded by the delta kernels, strings rebuilt by
+k_pq_dba_bytes, one wave per segment of values). With
 spark.auron.scan.deltaNative.enable off, DELTA_BINARY_PACKED pages are
-expanded to PLAIN by a host job per page and DELTA_LENGTH_BYTE_ARRAY
-columns fall back to pyarrow. DELTA_BYTE_ARRAY always falls back.
+expanded to PLAIN by a host job per page and DELTA_LENGTH_BYTE_ARRAY and
+DELTA_BYTE_ARRAY columns fall back to pyarrow.
 """
 from __future__ import annotations
 
@@ -161,7 +163,8 @@ class PageDesc:
     values_len: int
     row_start: int
     # 0=PLAIN, 8=RLE_DICTIONARY (PLAIN_DICTIONARY folded in),
-    # 5=DELTA_BINARY_PACKED, 6=DELTA_LENGTH_BYTE_ARRAY (device-decoded)
+    # 5=DELTA_BINARY_PACKED, 6=DELTA_LENGTH_BYTE_ARRAY,
+    # 7=DELTA_BYTE_ARRAY (device-decoded)
     encoding: int = 0
 
 
@@ -189,6 +192,9 @@ class ChunkPages:
     # host-built DELTA_BINARY_PACKED block/miniblock index of all pages
     # (delta_index); cached so HBM-cache hits never need the host buffer
     delta_idx: Optional["DeltaIndex"] = None
+    # DELTA_BYTE_ARRAY only: delta_idx indexes the prefix-length streams,
+    # delta_idx2 the suffix-length streams that follow them
+    delta_idx2: Optional["DeltaIndex"] = None
 
     @property
     def is_dict(self) -> bool:
@@ -247,16 +253,16 @@ def parse_pages(buf: np.ndarray, chunk_off: int, chunk_len: int,
     dictionary and plain data pages fall back to the host path.
 
     With `delta_native`, DELTA_BINARY_PACKED pages of INT32/INT64 chunks
-    and DELTA_LENGTH_BYTE_ARRAY pages of BYTE_ARRAY chunks keep their
-    encoding (5 / 6) for the device decode; without it encoding 5 becomes
-    a host "delta" job that expands the page to PLAIN, and encoding 6 is
-    rejected."""
+    and DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY pages of BYTE_ARRAY
+    chunks keep their encoding (5 / 6 / 7) for the device decode; without
+    it encoding 5 becomes a host "delta" job that expands the page to
+    PLAIN, and encodings 6 and 7 are rejected."""
     delta_encs = ()
     if delta_native:
         if phys in ("INT32", "INT64"):
             delta_encs = (5,)
         elif phys == "BYTE_ARRAY":
-            delta_encs = (6,)
+            delta_encs = (6, 7)
     mv = memoryview(buf)
     pos = chunk_off
     end = chunk_off + chunk_len
@@ -390,7 +396,7 @@ def parse_pages(buf: np.ndarray, chunk_off: int, chunk_len: int,
         return None
     if encs == {8} and ck.dict_off < 0:
         return None
-    if encs & {5, 6} and ck.dict_off >= 0:
+    if encs & {5, 6, 7} and ck.dict_off >= 0:
         return None  # dictionary page + delta data pages -> host fallback
     return ck
 
@@ -498,9 +504,10 @@ def parse_plain_strings(buf: np.ndarray, ck: ChunkPages) -> None:
 # present values decoded per path: DELTA_BINARY_PACKED columns by the
 # k_pq_delta_* kernels / on the host (delta_decode_ref on CPU reads,
 # au_host_delta_unpack jobs with the switch off), and strings whose
-# DELTA_LENGTH_BYTE_ARRAY lengths went through the delta decode
+# DELTA_LENGTH_BYTE_ARRAY lengths went through the delta decode, and
+# DELTA_BYTE_ARRAY strings rebuilt from delta-decoded prefix/suffix lengths
 STATS = {"delta_values_device": 0, "delta_values_host": 0,
-         "delta_length_strings": 0}
+         "delta_length_strings": 0, "delta_byte_array_strings": 0}
 
 
 def delta_native_enabled() -> bool:
@@ -654,9 +661,186 @@ def delta_decode(dbuf: torch.Tensor, index: DeltaIndex, esize: int, device,
 
 
 def _chunk_delta_index(buf: np.ndarray, ck: ChunkPages) -> None:
-    if ck.delta_idx is None:
-        ck.delta_idx = delta_index(
-            buf, [(p.values_off, p.values_len, p.n_values) for p in ck.pages])
+    if ck.delta_idx is not None:
+        return
+    pages = [(p.values_off, p.values_len, p.n_values) for p in ck.pages]
+    if ck.pages[0].encoding == 7:
+        ck.delta_idx, ck.delta_idx2 = delta_byte_array_index(buf, pages)
+    else:
+        ck.delta_idx = delta_index(buf, pages)
+
+
+# ---------------------------------------------------- DELTA_BYTE_ARRAY
+# Values per wave of k_pq_dba_bytes. A wave pays one dependent
+# load -> store round trip per value of its segment, plus a seed walk that
+# reads 64 prefix lengths per step back to the last value with prefix 0
+# (for sorted keys: the page start, up to 20000 values in a pyarrow page).
+# Smaller segments give more waves but repeat that walk more often. At 256
+# a row group of 2^20 values is 4096 waves, half the wave slots of the 256
+# CUs, and the forward pass (256 steps) is the same order as the walk (at
+# most page values / 64 steps), so neither side dominates. The scan time
+# is flat from 64 to 1024 and 7% worse at 4096 (profiles/README.md).
+DBA_SEG_VALUES = 256
+
+_DBA_CORRUPT = "corrupt DELTA_BYTE_ARRAY page: "
+_DBA_BAD_LENGTHS = _DBA_CORRUPT + (
+    "negative length, first prefix not 0, prefix longer than the previous "
+    "string, suffix lengths that do not fill the page, or a value count "
+    "that disagrees with the levels")
+
+
+def dba_tile() -> int:
+    """Bytes of the 'current string' one wave of k_pq_dba_bytes holds."""
+    from . import native
+
+    return int(native.host_lib().au_pq_dba_tile())
+
+
+def delta_byte_array_index(buf: np.ndarray, pages):
+    """Index the DELTA_BYTE_ARRAY pages at `pages` (triples as for
+    delta_index) -> (prefix-length index, suffix-length index). A page's
+    suffix-length stream starts where its prefix-length stream ends; the
+    suffix bytes follow it. Raises ValueError on a corrupt stream or when
+    the two header totals of a page differ."""
+    pidx = delta_index(buf, pages)
+    sidx = delta_index(buf, [
+        (int(e), off + ln - int(e), n)
+        for (off, ln, n), e in zip(pages, pidx.pg[:, 2])])
+    _dba_check_totals(pidx, sidx)
+    return pidx, sidx
+
+
+def _dba_check_totals(pidx: DeltaIndex, sidx: DeltaIndex) -> None:
+    if len(pidx.pg) != len(sidx.pg) or \
+            (pidx.pg[:, 1] != sidx.pg[:, 1]).any():
+        raise ValueError(_DBA_CORRUPT + "prefix and suffix length streams "
+                         "hold different numbers of values")
+
+
+def _page_value_starts_np(lens: np.ndarray, pg: np.ndarray,
+                          page_ends: np.ndarray):
+    """Byte layout shared by encodings 6 and 7: a page's values lie back to
+    back behind the length stream that `pg` (DeltaIndex.pg) describes, so a
+    value starts at the stream end plus the exclusive sum of the page's
+    lengths before it. -> (absolute start per value, ok); ok is False when
+    a length is negative or a page's lengths do not add up to exactly the
+    bytes between the stream end and `page_ends`."""
+    page_bytes = page_ends - pg[:, 2]
+    run = np.cumsum(lens)
+    excl = run - lens
+    live = pg[:, 1] > 0
+    first = np.zeros(len(pg), dtype=np.int64)
+    first[live] = excl[pg[live, 3]]
+    sums = np.zeros(len(pg), dtype=np.int64)
+    sums[live] = run[pg[live, 3] + pg[live, 1] - 1] - first[live]
+    ok = not ((lens < 0).any() or (sums != page_bytes).any())
+    starts = excl + np.repeat(pg[:, 2] - first, pg[:, 1])
+    return starts, ok
+
+
+def _page_value_starts_gpu(lens_t: torch.Tensor, pg: np.ndarray,
+                           page_ends: np.ndarray, device):
+    """Device form of _page_value_starts_np, no host sync: -> (absolute
+    start per value int64, bad flag). With no value at all it returns one
+    dummy start so that a clamped row lookup has something to read."""
+    n = int(lens_t.numel())
+    page_bytes = page_ends - pg[:, 2]
+    if n == 0:
+        return (torch.zeros(1, dtype=torch.int64, device=device),
+                torch.from_numpy(page_bytes != 0).any().to(device))
+    # per-page constants, one small upload: stream end, compact base,
+    # index of the last value, bytes left after the stream, live flag
+    live = pg[:, 1] > 0
+    consts = np.stack([pg[:, 2], np.minimum(pg[:, 3], n - 1),
+                       np.clip(pg[:, 3] + pg[:, 1] - 1, 0, n - 1),
+                       page_bytes, live.astype(np.int64), pg[:, 1]])
+    dc = _pin_to_device(consts.reshape(-1), device).view(torch.int64) \
+        .view(6, len(pg))
+    run = torch.cumsum(lens_t, 0)
+    excl = run - lens_t
+    first = excl[dc[1]]
+    sums = (run[dc[2]] - first) * dc[4]
+    pid = torch.repeat_interleave(
+        torch.arange(len(pg), dtype=torch.int64, device=device), dc[5],
+        output_size=n)
+    offs_t = excl + (dc[0] - first)[pid]
+    bad = (sums != dc[3]).any() | (lens_t < 0).any()
+    return offs_t, bad
+
+
+def delta_byte_array_decode_ref(buf: np.ndarray, pidx: DeltaIndex,
+                                sidx: DeltaIndex, page_ends: np.ndarray):
+    """Host decode of an indexed DELTA_BYTE_ARRAY chunk -> (data uint8,
+    offsets int64[n+1]) of the compact stream of present values. Lengths
+    from delta_decode_ref, the serial reconstruction by au_host_dba_decode;
+    same checks as the device path. Oracle for k_pq_dba_bytes and the CPU
+    read path."""
+    from . import native
+
+    _dba_check_totals(pidx, sidx)
+    page_ends = np.asarray(page_ends, dtype=np.int64)
+    n = pidx.total
+    P = delta_decode_ref(buf, pidx, 4).astype(np.int64)
+    S = delta_decode_ref(buf, sidx, 4).astype(np.int64)
+    so, ok = _page_value_starts_np(S, sidx.pg, page_ends)
+    L = P + S
+    if n:
+        ok = ok and not (P < 0).any() and P[0] == 0 \
+            and not (P[1:] > L[:-1]).any()
+    if not ok:
+        raise ValueError(_DBA_BAD_LENGTHS)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(L, out=offsets[1:])
+    data = np.empty(int(offsets[-1]), dtype=np.uint8)
+    buf = np.ascontiguousarray(buf)
+    so = np.ascontiguousarray(so)
+    rc = native.host_lib().au_host_dba_decode(
+        buf.ctypes.data, buf.size, P.ctypes.data, S.ctypes.data,
+        so.ctypes.data, offsets.ctypes.data, n, data.ctypes.data, data.size)
+    if rc != 0:
+        raise ValueError(_DBA_BAD_LENGTHS)
+    return data, offsets
+
+
+def delta_byte_array_decode(dbuf: torch.Tensor, pidx: DeltaIndex,
+                            sidx: DeltaIndex, page_ends: np.ndarray, device,
+                            seg: Optional[int] = None, also_bad=None):
+    """Device decode of an indexed DELTA_BYTE_ARRAY chunk -> (data uint8,
+    offsets int64[n+1]) of the compact stream of present values: two
+    delta_decode runs for the lengths, torch scans for the offsets, one
+    host sync that reads (total bytes, bad) and then k_pq_dba_bytes. The
+    kernel checks nothing, so nothing is launched unless the lengths are
+    sane; `also_bad` is a further device flag for that one sync. `seg`
+    (default DBA_SEG_VALUES) is the number of values per wave."""
+    from . import native
+
+    lib = native.require()
+    _dba_check_totals(pidx, sidx)
+    page_ends = np.asarray(page_ends, dtype=np.int64)
+    seg = DBA_SEG_VALUES if seg is None else int(seg)
+    if seg < 1:
+        raise ValueError(f"segment of {seg} values")
+    n = pidx.total
+    P = delta_decode(dbuf, pidx, 4, device).to(torch.int64)
+    S = delta_decode(dbuf, sidx, 4, device).to(torch.int64)
+    so, bad = _page_value_starts_gpu(S, sidx.pg, page_ends, device)
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    if n:
+        L = P + S
+        bad = bad | (P < 0).any() | (P[0] != 0) | (P[1:] > L[:-1]).any()
+        torch.cumsum(L, 0, out=offsets[1:])
+    if also_bad is not None:
+        bad = bad | also_bad
+    total, is_bad = torch.stack([offsets[-1], bad.to(torch.int64)]).tolist()
+    if is_bad:
+        raise ValueError(_DBA_BAD_LENGTHS)
+    data = torch.empty(total, dtype=torch.uint8, device=device)
+    if total:
+        rc = lib.au_pq_dba_bytes(P.data_ptr(), S.data_ptr(), so.data_ptr(),
+                                 offsets.data_ptr(), n, seg, dbuf.data_ptr(),
+                                 data.data_ptr(), native.stream_ptr(device))
+        native.check(rc, "au_pq_dba_bytes")
+    return data, offsets
 
 
 def _validity_np(buf: np.ndarray, pages: List[PageDesc],
@@ -1175,7 +1359,7 @@ def read_columns_native(path: str, columns: List[str], device,
             # the def-level runs below
             for cm in meta.cols:
                 for ck in cm.pages:
-                    if ck.pages[0].encoding in (5, 6):
+                    if ck.pages[0].encoding in (5, 6, 7):
                         _chunk_delta_index(buf, ck)
             meta.delta_indexed = True
 
@@ -1199,7 +1383,7 @@ def read_columns_native(path: str, columns: List[str], device,
                     if cm.phys == "BYTE_ARRAY":
                         if ck.is_dict:
                             parse_dict_strings(buf, ck)
-                        elif ck.pages[0].encoding != 6:
+                        elif ck.pages[0].encoding not in (6, 7):
                             parse_plain_strings(buf, ck)
                     if ck.is_dict and ck.idx_bws is None:
                         ck.idx_bws = [int(buf[p.values_off]) for p in ck.pages]
@@ -1370,6 +1554,53 @@ def _decode_chunk_plain_strings(buf, dbuf, ck: ChunkPages, num_values: int,
                              num_values, device, chunk_nulls)
 
 
+def _page_ends(ck: ChunkPages) -> np.ndarray:
+    return np.array([p.values_off + p.values_len for p in ck.pages],
+                    dtype=np.int64)
+
+
+def _decode_chunk_dba_strings(buf, dbuf, ck: ChunkPages, num_values: int,
+                              device, use_gpu: bool,
+                              chunk_nulls: bool) -> Column:
+    """DELTA_BYTE_ARRAY chunk -> string Column. The decode yields the
+    compact stream of present values; NULL rows have length 0, so its
+    bytes are the column's data as they are and only the row offsets are
+    routed through the validity prefix sum."""
+    pidx, sidx = ck.delta_idx, ck.delta_idx2
+    n = pidx.total
+    page_ends = _page_ends(ck)
+    if not use_gpu:
+        validity = _validity_np(buf, ck.pages, num_values)
+        _check_delta_counts(ck, validity)
+        data, compact = delta_byte_array_decode_ref(buf, pidx, sidx,
+                                                    page_ends)
+        STATS["delta_byte_array_strings"] += n
+        offsets = compact
+        vt = None
+        if validity is not None:
+            offsets = np.zeros(num_values + 1, dtype=np.int64)
+            offsets[1:] = compact[np.cumsum(validity, dtype=np.int64)]
+            if chunk_nulls and not validity.all():
+                vt = torch.from_numpy(validity.astype(bool))
+        return Column(dtypes.string, torch.from_numpy(data), vt,
+                      torch.from_numpy(offsets))
+    validity, prefix = _gpu_validity_prefix(dbuf, ck.pages, num_values, device,
+                                            chunk_nulls, ck.runs_np)
+    if validity is None and n != num_values:
+        raise ValueError(_DBA_CORRUPT + "header totals disagree with the "
+                         "row count")
+    data, compact = delta_byte_array_decode(
+        dbuf, pidx, sidx, page_ends, device,
+        also_bad=(prefix[-1] != n) if prefix is not None else None)
+    STATS["delta_byte_array_strings"] += n
+    if prefix is None:
+        return Column(dtypes.string, data, None, compact)
+    offsets = torch.zeros(num_values + 1, dtype=torch.int64, device=device)
+    torch.index_select(compact, 0, prefix, out=offsets[1:])
+    vt = validity.to(torch.bool) if chunk_nulls else None
+    return Column(dtypes.string, data, vt, offsets)
+
+
 def _decode_chunk_delta_strings(buf, dbuf, ck: ChunkPages, num_values: int,
                                 device, use_gpu: bool,
                                 chunk_nulls: bool) -> Column:
@@ -1380,23 +1611,15 @@ def _decode_chunk_delta_strings(buf, dbuf, ck: ChunkPages, num_values: int,
     exactly the bytes left in it."""
     idx = ck.delta_idx
     pg = idx.pg
-    page_bytes = np.array([p.values_off + p.values_len for p in ck.pages],
-                          dtype=np.int64) - pg[:, 2]
+    page_ends = _page_ends(ck)
     if not use_gpu:
         lens = delta_decode_ref(buf, idx, 4).astype(np.int64)
         validity = _validity_np(buf, ck.pages, num_values)
         _check_delta_counts(ck, validity)
-        run = np.cumsum(lens)
-        excl = run - lens
-        live = pg[:, 1] > 0
-        first = np.zeros(len(pg), dtype=np.int64)
-        first[live] = excl[pg[live, 3]]
-        sums = np.zeros(len(pg), dtype=np.int64)
-        sums[live] = run[pg[live, 3] + pg[live, 1] - 1] - first[live]
-        if (lens < 0).any() or (sums != page_bytes).any():
+        starts, ok = _page_value_starts_np(lens, pg, page_ends)
+        if not ok:
             raise ValueError("corrupt DELTA_LENGTH_BYTE_ARRAY page: lengths "
                              "do not add up to the page's bytes")
-        starts = excl + np.repeat(pg[:, 2] - first, pg[:, 1])
         STATS["delta_length_strings"] += idx.total
         return _strings_tail_np(buf, starts, lens, validity, num_values,
                                 chunk_nulls)
@@ -1407,27 +1630,9 @@ def _decode_chunk_delta_strings(buf, dbuf, ck: ChunkPages, num_values: int,
                          "totals disagree with the row count")
     lens_t = delta_decode(dbuf, idx, 4, device).to(torch.int64)
     n = idx.total
-    # per-page constants, one small upload: stream end, compact base,
-    # index of the last value, bytes left after the stream, live flag
-    live = pg[:, 1] > 0
-    consts = np.stack([pg[:, 2], np.minimum(pg[:, 3], max(n - 1, 0)),
-                       np.clip(pg[:, 3] + pg[:, 1] - 1, 0, max(n - 1, 0)),
-                       page_bytes, live.astype(np.int64), pg[:, 1]])
-    dc = _pin_to_device(consts.reshape(-1), device).view(torch.int64) \
-        .view(6, len(pg))
-    if n:
-        run = torch.cumsum(lens_t, 0)
-        excl = run - lens_t
-        first = excl[dc[1]]
-        sums = (run[dc[2]] - first) * dc[4]
-        pid = torch.repeat_interleave(
-            torch.arange(len(pg), dtype=torch.int64, device=device), dc[5],
-            output_size=n)
-        offs_t = excl + (dc[0] - first)[pid]
-        bad = (sums != dc[3]).any() | (lens_t < 0).any()
-    else:  # all-NULL chunk: one dummy entry for the clamped row lookup
-        offs_t = lens_t = torch.zeros(1, dtype=torch.int64, device=device)
-        bad = torch.from_numpy(page_bytes != 0).any().to(device)
+    offs_t, bad = _page_value_starts_gpu(lens_t, pg, page_ends, device)
+    if n == 0:  # all-NULL chunk: one dummy entry for the clamped row lookup
+        lens_t = torch.zeros(1, dtype=torch.int64, device=device)
     if prefix is not None:
         bad = bad | (prefix[-1] != n)
     STATS["delta_length_strings"] += n
@@ -1483,6 +1688,9 @@ def _decode_chunk_strings(buf, dbuf, ck: ChunkPages, num_values: int, device,
     if ck.pages[0].encoding == 6:
         return _decode_chunk_delta_strings(buf, dbuf, ck, num_values, device,
                                            use_gpu, chunk_nulls)
+    if ck.pages[0].encoding == 7:
+        return _decode_chunk_dba_strings(buf, dbuf, ck, num_values, device,
+                                         use_gpu, chunk_nulls)
     if not ck.is_dict:
         return _decode_chunk_plain_strings(buf, dbuf, ck, num_values, device,
                                            use_gpu, chunk_nulls)
