@@ -140,6 +140,15 @@ STREAM_JOIN_PROBE = _opt("spark.auron.stream.joinProbe.enable", True, bool,
                          "probe build-right joins batch-by-batch on the "
                          "streaming path (GPU only)",
                          env="AURON_STREAM_JOIN_PROBE")
+JOIN_FUSED_PROBE = _opt("spark.auron.join.fusedProbe.enable", True, bool,
+                        "probe hash joins with the fused kernels "
+                        "(k_join_probe_count / k_join_probe_fill / "
+                        "k_join_exists: probe hash computed in-kernel, one "
+                        "chain walk, per-tile offsets, key descriptors passed "
+                        "by value) for up to 8 key columns (off: murmur3 + "
+                        "k_join_count + torch scan + k_join_fill, and "
+                        "join_counts for semi/anti/existence joins)",
+                        env="AURON_JOIN_FUSED_PROBE")
 SPILL_DIR = _opt("spark.auron.spill.dir", "", str,
                  "directory for disk-tier spill files (empty = system tmp)",
                  env="AURON_SPILL_DIR")

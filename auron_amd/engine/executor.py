@@ -2052,12 +2052,13 @@ class Executor:
                                            node.residual, node.existence_col)
 
         if how in ("semi", "anti", "existence"):
-            counts = ops.join_counts(rkeys, lkeys)  # build=right, probe=left
+            # build=right, probe=left; reuses the broadcast cache's table
+            matched = ops.join_exists(rkeys, lkeys, table=table)
             if how == "semi":
-                return [left.filter(counts > 0)]
+                return [left.filter(matched)]
             if how == "anti":
-                return [left.filter(counts == 0)]
-            exists = Column(dtypes.bool_, counts > 0)
+                return [left.filter(~matched)]
+            exists = Column(dtypes.bool_, matched)
             return [RecordBatch(left.names + [node.existence_col], left.columns + [exists])]
 
         preserved = {"inner": set(), "left": {"left"}, "right": {"right"},

@@ -211,24 +211,29 @@ def all_to_all(batches_by_dest: List[Optional[RecordBatch]], device,
         )
         out_batches = _split_recv_flat(recv_flat, recv_sizes, recv_metas)
     else:
-        # pairwise deterministic schedule (gloo CPU CI path)
+        # pairwise deterministic schedule (gloo CPU CI path). gloo's
+        # send/recv take the tensor's raw pointer and know no stream, so
+        # device buffers are staged through host memory: .cpu() waits for
+        # the kernels that packed the buffer, .to(device) orders the upload
+        # before its consumers
         recv_bufs: List[Optional[torch.Tensor]] = [None] * world
         recv_bufs[rank] = bufs[rank]
         for other in range(world):
             if other == rank:
                 continue
-            rb = torch.empty(recv_sizes[other], dtype=torch.uint8, device=device)
+            sb = bufs[other].cpu()
+            rb = torch.empty(recv_sizes[other], dtype=torch.uint8)
             if rank < other:
-                if bufs[other].numel():
-                    dist.send(bufs[other], dst=other, group=group)
+                if sb.numel():
+                    dist.send(sb, dst=other, group=group)
                 if rb.numel():
                     dist.recv(rb, src=other, group=group)
             else:
                 if rb.numel():
                     dist.recv(rb, src=other, group=group)
-                if bufs[other].numel():
-                    dist.send(bufs[other], dst=other, group=group)
-            recv_bufs[other] = rb
+                if sb.numel():
+                    dist.send(sb, dst=other, group=group)
+            recv_bufs[other] = rb.to(device)
         for s in range(world):
             if recv_metas[s] is not None:
                 out_batches.append(unpack_batch(recv_metas[s], recv_bufs[s]))
@@ -263,13 +268,15 @@ def all_gather_batch(batch: Optional[RecordBatch], device, group=None) -> List[R
     all_meta = [g[0] for g in gathered]
     sizes = [g[1] for g in gathered]
     maxsz = max(sizes) if sizes else 0
-    padded = torch.zeros(max(maxsz, 1), dtype=torch.uint8, device=device)
+    # gloo gathers in host memory (see all_to_all); nccl on the device
+    comm_dev = device if dist.get_backend(group) == "nccl" else "cpu"
+    padded = torch.zeros(max(maxsz, 1), dtype=torch.uint8, device=comm_dev)
     if buf.numel():
         padded[:buf.numel()].copy_(buf)
-    outs = [torch.empty(max(maxsz, 1), dtype=torch.uint8, device=device) for _ in range(world)]
+    outs = [torch.empty(max(maxsz, 1), dtype=torch.uint8, device=comm_dev) for _ in range(world)]
     dist.all_gather(outs, padded, group=group)
     res = []
     for s in range(world):
         if all_meta[s] is not None:
-            res.append(unpack_batch(all_meta[s], outs[s][:sizes[s]]))
+            res.append(unpack_batch(all_meta[s], outs[s][:sizes[s]].to(device)))
     return res

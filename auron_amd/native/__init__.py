@@ -52,6 +52,17 @@ def _try_load():
     lib.au_join_build.argtypes = [i64, c, i64, c, c, c]
     lib.au_join_count.argtypes = [c, c, ctypes.c_int, i64, c, i64, c, c, c, c]
     lib.au_join_fill.argtypes = [c, c, ctypes.c_int, i64, c, i64, c, c, c, c, c, c, ctypes.c_int, c]
+    lib.au_join_probe_tile.argtypes = []
+    lib.au_join_probe_tile.restype = i64
+    lib.au_join_probe_max_keys.argtypes = []
+    lib.au_join_probe_max_keys.restype = ctypes.c_int
+    lib.au_join_probe_count.argtypes = [c, ctypes.c_int, i64, c, i64, c, i32,
+                                        ctypes.c_int, c, c, c, c, c]
+    lib.au_join_probe_fill.argtypes = [c, ctypes.c_int, i64, c, c, c, c,
+                                       ctypes.c_int, c, c, c]
+    lib.au_join_exists.argtypes = [c, ctypes.c_int, i64, c, i64, c, i32, c, c]
+    for f in ("au_join_probe_count", "au_join_probe_fill", "au_join_exists"):
+        getattr(lib, f).restype = ctypes.c_int
     lib.au_pmod.argtypes = [c, i64, i32, c, c]
     lib.au_bytes_gather.argtypes = [c, c, c, c, i64, c]
     lib.au_multi_gather.argtypes = [c, i64, c, ctypes.c_int, c]
@@ -159,12 +170,13 @@ _DESC_DTYPE = np.dtype(
 assert _DESC_DTYPE.itemsize == 32
 
 
-def pack_descs(cols, device) -> Tuple[torch.Tensor, list]:
-    """Pack Column descriptors into a device uint8 tensor (AuColDesc[]).
+def pack_descs_host(cols) -> Tuple[np.ndarray, list]:
+    """Pack Column descriptors into a host numpy array (AuColDesc[]) without
+    uploading it: for kernels that take their descriptors by value in the
+    kernel arguments (au_join_probe_*).
 
-    Returns (desc_tensor, keepalive). Caller must hold `keepalive` until the
-    kernels using the descriptors have been enqueued (torch stream ordering
-    then keeps buffers alive until completion).
+    Returns (desc_array, keepalive); `keepalive` holds the contiguous buffers
+    the descriptors point into (see pack_descs).
     """
     n = len(cols)
     arr = np.zeros(n, dtype=_DESC_DTYPE)
@@ -185,6 +197,17 @@ def pack_descs(cols, device) -> Tuple[torch.Tensor, list]:
             arr[i]["validity"] = v.data_ptr()
         arr[i]["dtype"] = col.dtype.code
         arr[i]["scale"] = col.dtype.scale
+    return arr, keep
+
+
+def pack_descs(cols, device) -> Tuple[torch.Tensor, list]:
+    """Pack Column descriptors into a device uint8 tensor (AuColDesc[]).
+
+    Returns (desc_tensor, keepalive). Caller must hold `keepalive` until the
+    kernels using the descriptors have been enqueued (torch stream ordering
+    then keeps buffers alive until completion).
+    """
+    arr, keep = pack_descs_host(cols)
     from ..pinned import to_device
 
     dev = to_device(arr.view(np.uint8).reshape(-1), device)

@@ -387,6 +387,302 @@ AU_EXPORT int au_join_fill(const void* bcols, const void* pcols, int ncols,
   return (int)hipGetLastError();
 }
 
+// ---------------------------------------------------------- fused join probe
+// count -> torch glue -> fill, folded into two kernels: the probe hash is
+// computed in-kernel (same seed chaining as k_murmur3), the chain is walked
+// once, and output offsets come from a per-tile sum plus an in-block scan
+// instead of N-sized int64 temporaries. Key descriptors travel by value in
+// the kernel-argument struct (as MgParams does), so no descriptor upload and
+// no per-row descriptor load from global memory.
+//
+// Rows are handled in fixed tiles: tile t covers [t*JP_TILE, (t+1)*JP_TILE),
+// row = tile_base + slab*256 + tid. Everything is indexed by tile, never by
+// block, so the row -> output mapping does not depend on the grid.
+#define JP_MAX_KEYS 8
+#define JP_BLOCK 256
+#define JP_SLABS 4
+#define JP_TILE (JP_BLOCK * JP_SLABS)
+
+struct JpKeys {
+  AuColDesc build[JP_MAX_KEYS];
+  AuColDesc probe[JP_MAX_KEYS];
+};
+
+// MODE 0: any key shape (hash_one / keys_equal per column)
+// MODE 1: exactly one int64 / decimal64 / timestamp key
+// MODE 2: exactly one int32 / date32 key
+// pkey carries the probe key of the integer modes; MODE 0 ignores it.
+template <int MODE>
+__device__ __forceinline__ bool jp_probe_key(const JpKeys& k, int ncols,
+                                             int64_t i, int64_t* pkey) {
+  if (MODE == 0) return !join_row_has_null(k.probe, ncols, i);
+  const uint8_t* v = k.probe[0].validity;
+  if (v != nullptr && v[i] == 0) return false;
+  if (MODE == 1) *pkey = ((const int64_t*)k.probe[0].data)[i];
+  else *pkey = ((const int32_t*)k.probe[0].data)[i];
+  return true;
+}
+
+template <int MODE>
+__device__ __forceinline__ uint32_t jp_hash(const JpKeys& k, int ncols,
+                                            int64_t i, int64_t pkey,
+                                            uint32_t seed) {
+  if (MODE == 1) return hash_long((uint64_t)pkey, seed);
+  if (MODE == 2) return hash_int((uint32_t)(int32_t)pkey, seed);
+  uint32_t h = seed;
+  for (int c = 0; c < ncols; c++) h = hash_one(k.probe[c], i, h);  // no NULLs here
+  return h;
+}
+
+template <int MODE>
+__device__ __forceinline__ bool jp_match(const JpKeys& k, int ncols, int32_t j,
+                                         int64_t i, int64_t pkey) {
+  if (MODE == 0)
+    return keys_equal(k.build, j, k.probe, i, ncols) &&
+           !join_row_has_null(k.build, ncols, j);
+  const uint8_t* v = k.build[0].validity;
+  if (MODE == 1) {
+    if (((const int64_t*)k.build[0].data)[j] != pkey) return false;
+  } else {
+    if (((const int32_t*)k.build[0].data)[j] != (int32_t)pkey) return false;
+  }
+  return v == nullptr || v[j] != 0;
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(JP_BLOCK) k_join_probe_count(
+    JpKeys k, int ncols, int64_t n_probe, int64_t n_tiles,
+    const int32_t* __restrict__ heads, uint32_t cap_mask,
+    const int32_t* __restrict__ next, uint32_t seed, int emit_unmatched_probe,
+    int32_t* __restrict__ counts, int32_t* __restrict__ first,
+    int64_t* __restrict__ tile_sums, uint8_t* build_matched) {
+  __shared__ int64_t wsum[JP_BLOCK / 64];
+  const int tid = threadIdx.x;
+  for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const int64_t base = t * JP_TILE;
+    // heads of all slabs first: the loads are independent, so they overlap
+    int32_t j0[JP_SLABS];
+    int64_t pk[JP_SLABS];
+#pragma unroll
+    for (int s = 0; s < JP_SLABS; s++) {
+      const int64_t i = base + s * JP_BLOCK + tid;
+      j0[s] = -1;
+      pk[s] = 0;
+      if (i < n_probe && jp_probe_key<MODE>(k, ncols, i, &pk[s]))
+        j0[s] = heads[jp_hash<MODE>(k, ncols, i, pk[s], seed) & cap_mask];
+    }
+    int64_t acc = 0;
+#pragma unroll
+    for (int s = 0; s < JP_SLABS; s++) {
+      const int64_t i = base + s * JP_BLOCK + tid;
+      if (i >= n_probe) continue;
+      int32_t cnt = 0, f = -1;
+      for (int32_t j = j0[s]; j != -1; j = next[j]) {
+        if (jp_match<MODE>(k, ncols, j, i, pk[s])) {
+          if (cnt == 0) f = j;
+          cnt++;
+          if (build_matched) build_matched[j] = 1;
+        }
+      }
+      counts[i] = cnt;
+      first[i] = f;
+      acc += (emit_unmatched_probe && cnt == 0) ? 1 : cnt;
+    }
+    for (int d = 32; d > 0; d >>= 1) acc += __shfl_down(acc, d, 64);
+    if ((tid & 63) == 0) wsum[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) {
+      int64_t sum = 0;
+      for (int w = 0; w < JP_BLOCK / 64; w++) sum += wsum[w];
+      tile_sums[t] = sum;
+    }
+    __syncthreads();
+  }
+}
+
+// tile_ends = inclusive prefix sum of tile_sums (host: one cumsum over
+// n_tiles elements). Offsets inside a tile come from a block-exclusive scan
+// per slab (wave scan + LDS across the four waves) with the running base
+// carried from slab to slab. cnt == 1 rows never touch the table or a key.
+template <int MODE>
+__global__ void __launch_bounds__(JP_BLOCK) k_join_probe_fill(
+    JpKeys k, int ncols, int64_t n_probe, int64_t n_tiles,
+    const int32_t* __restrict__ next, const int32_t* __restrict__ counts,
+    const int32_t* __restrict__ first, const int64_t* __restrict__ tile_ends,
+    int emit_unmatched_probe, int64_t* __restrict__ build_out,
+    int64_t* __restrict__ probe_out) {
+  // two buffers, alternating per slab: one barrier per slab is enough
+  __shared__ int64_t wtot[2][JP_BLOCK / 64];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const int64_t base = t * JP_TILE;
+    int64_t running = t == 0 ? 0 : tile_ends[t - 1];
+    for (int s = 0; s < JP_SLABS; s++) {
+      const int64_t i = base + s * JP_BLOCK + tid;
+      const bool in = i < n_probe;
+      const int32_t cnt = in ? counts[i] : 0;
+      const int64_t eff = !in ? 0 : (emit_unmatched_probe && cnt == 0) ? 1 : cnt;
+      int64_t incl = eff;
+      for (int d = 1; d < 64; d <<= 1) {
+        int64_t up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+      }
+      if (lane == 63) wtot[s & 1][wave] = incl;
+      __syncthreads();
+      int64_t before = 0, total = 0;
+      for (int w = 0; w < JP_BLOCK / 64; w++) {
+        const int64_t x = wtot[s & 1][w];
+        if (w < wave) before += x;
+        total += x;
+      }
+      int64_t o = running + before + incl - eff;
+      running += total;
+      if (!in) continue;
+      if (cnt == 0) {
+        if (emit_unmatched_probe) {
+          build_out[o] = -1;
+          probe_out[o] = i;
+        }
+      } else if (cnt == 1) {
+        build_out[o] = first[i];
+        probe_out[o] = i;
+      } else {
+        int64_t pkey = 0;
+        jp_probe_key<MODE>(k, ncols, i, &pkey);
+        int32_t left = cnt;
+        for (int32_t j = first[i]; j != -1 && left > 0; j = next[j]) {
+          if (jp_match<MODE>(k, ncols, j, i, pkey)) {
+            build_out[o] = j;
+            probe_out[o] = i;
+            o++;
+            left--;
+          }
+        }
+      }
+    }
+  }
+}
+
+// semi / anti / existence: stop at the first match, one byte per probe row
+template <int MODE>
+__global__ void __launch_bounds__(JP_BLOCK) k_join_exists(
+    JpKeys k, int ncols, int64_t n_probe, const int32_t* __restrict__ heads,
+    uint32_t cap_mask, const int32_t* __restrict__ next, uint32_t seed,
+    uint8_t* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_probe;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    uint8_t found = 0;
+    int64_t pkey = 0;
+    if (jp_probe_key<MODE>(k, ncols, i, &pkey)) {
+      int32_t j = heads[jp_hash<MODE>(k, ncols, i, pkey, seed) & cap_mask];
+      while (j != -1) {
+        if (jp_match<MODE>(k, ncols, j, i, pkey)) {
+          found = 1;
+          break;
+        }
+        j = next[j];
+      }
+    }
+    out[i] = found;
+  }
+}
+
+static inline bool jp_int64_family(int32_t d) {
+  return d == AU_INT64 || d == AU_DECIMAL64 || d == AU_TIMESTAMP;
+}
+static inline bool jp_int32_family(int32_t d) {
+  return d == AU_INT32 || d == AU_DATE32;
+}
+
+// host_descs: AuColDesc[2 * ncols] in host memory, build keys then probe keys
+static int jp_pack(const void* host_descs, int ncols, JpKeys* k) {
+  const AuColDesc* d = (const AuColDesc*)host_descs;
+  for (int c = 0; c < ncols; c++) {
+    k->build[c] = d[c];
+    k->probe[c] = d[ncols + c];
+  }
+  if (ncols == 1) {
+    if (jp_int64_family(d[0].dtype) && jp_int64_family(d[1].dtype)) return 1;
+    if (jp_int32_family(d[0].dtype) && jp_int32_family(d[1].dtype)) return 2;
+  }
+  return 0;
+}
+
+static inline int jp_grid(int64_t n_tiles) {
+  return (int)(n_tiles > 2048 ? 2048 : n_tiles);
+}
+
+AU_EXPORT int64_t au_join_probe_tile() { return JP_TILE; }
+AU_EXPORT int au_join_probe_max_keys() { return JP_MAX_KEYS; }
+
+AU_EXPORT int au_join_probe_count(const void* host_descs, int ncols,
+                                  int64_t n_probe, const int32_t* heads,
+                                  int64_t cap, const int32_t* next,
+                                  int32_t seed, int emit_unmatched_probe,
+                                  int32_t* counts, int32_t* first,
+                                  int64_t* tile_sums, uint8_t* build_matched,
+                                  void* stream) {
+  if (n_probe == 0) return 0;
+  if (ncols < 1 || ncols > JP_MAX_KEYS) return 1002;
+  JpKeys k{};
+  const int mode = jp_pack(host_descs, ncols, &k);
+  const int64_t n_tiles = (n_probe + JP_TILE - 1) / JP_TILE;
+#define JP_LAUNCH_COUNT(M)                                                     \
+  hipLaunchKernelGGL(k_join_probe_count<M>, dim3(jp_grid(n_tiles)),            \
+                     dim3(JP_BLOCK), 0, (hipStream_t)stream, k, ncols, n_probe, \
+                     n_tiles, heads, (uint32_t)(cap - 1), next, (uint32_t)seed, \
+                     emit_unmatched_probe, counts, first, tile_sums,           \
+                     build_matched)
+  if (mode == 1) JP_LAUNCH_COUNT(1);
+  else if (mode == 2) JP_LAUNCH_COUNT(2);
+  else JP_LAUNCH_COUNT(0);
+#undef JP_LAUNCH_COUNT
+  return (int)hipGetLastError();
+}
+
+AU_EXPORT int au_join_probe_fill(const void* host_descs, int ncols,
+                                 int64_t n_probe, const int32_t* next,
+                                 const int32_t* counts, const int32_t* first,
+                                 const int64_t* tile_ends,
+                                 int emit_unmatched_probe, int64_t* build_out,
+                                 int64_t* probe_out, void* stream) {
+  if (n_probe == 0) return 0;
+  if (ncols < 1 || ncols > JP_MAX_KEYS) return 1002;
+  JpKeys k{};
+  const int mode = jp_pack(host_descs, ncols, &k);
+  const int64_t n_tiles = (n_probe + JP_TILE - 1) / JP_TILE;
+#define JP_LAUNCH_FILL(M)                                                      \
+  hipLaunchKernelGGL(k_join_probe_fill<M>, dim3(jp_grid(n_tiles)),             \
+                     dim3(JP_BLOCK), 0, (hipStream_t)stream, k, ncols, n_probe, \
+                     n_tiles, next, counts, first, tile_ends,                  \
+                     emit_unmatched_probe, build_out, probe_out)
+  if (mode == 1) JP_LAUNCH_FILL(1);
+  else if (mode == 2) JP_LAUNCH_FILL(2);
+  else JP_LAUNCH_FILL(0);
+#undef JP_LAUNCH_FILL
+  return (int)hipGetLastError();
+}
+
+AU_EXPORT int au_join_exists(const void* host_descs, int ncols, int64_t n_probe,
+                             const int32_t* heads, int64_t cap,
+                             const int32_t* next, int32_t seed, uint8_t* out,
+                             void* stream) {
+  if (n_probe == 0) return 0;
+  if (ncols < 1 || ncols > JP_MAX_KEYS) return 1002;
+  JpKeys k{};
+  const int mode = jp_pack(host_descs, ncols, &k);
+#define JP_LAUNCH_EXISTS(M)                                                    \
+  hipLaunchKernelGGL(k_join_exists<M>, dim3(au_grid(n_probe, JP_BLOCK)),       \
+                     dim3(JP_BLOCK), 0, (hipStream_t)stream, k, ncols, n_probe, \
+                     heads, (uint32_t)(cap - 1), next, (uint32_t)seed, out)
+  if (mode == 1) JP_LAUNCH_EXISTS(1);
+  else if (mode == 2) JP_LAUNCH_EXISTS(2);
+  else JP_LAUNCH_EXISTS(0);
+#undef JP_LAUNCH_EXISTS
+  return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------- partitioning
 // part_id = pmod(murmur3_hash, nparts)  (Spark HashPartitioning semantics)
 __global__ void k_pmod(const int32_t* hashes, int64_t n, int32_t nparts,

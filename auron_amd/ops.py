@@ -287,6 +287,30 @@ def join_build(build_cols: List[Column]) -> Optional["JoinTable"]:
     return JoinTable(heads, nxt, cap, bhash, n_build)
 
 
+JOIN_PROBE_MAX_KEYS = 8  # JP_MAX_KEYS in kernels.hip (au_join_probe_max_keys)
+
+
+def _fused_probe_enabled() -> bool:
+    from .config import JOIN_FUSED_PROBE, AuronConf
+
+    return bool(AuronConf().get(JOIN_FUSED_PROBE))
+
+
+def join_probe_tile() -> int:
+    """Probe rows per tile of the fused probe kernels (JP_TILE)."""
+    return int(native.lib().au_join_probe_tile())
+
+
+def _join_key_descs(build_cols, probe_cols):
+    """Host AuColDesc[2 * ncols], build keys then probe keys, for the
+    kernels that take key descriptors by value."""
+    import numpy as np
+
+    barr, bkeep = native.pack_descs_host(build_cols)
+    parr, pkeep = native.pack_descs_host(probe_cols)
+    return np.concatenate([barr, parr]), (bkeep, pkeep)
+
+
 def hash_join(build_cols: List[Column], probe_cols: List[Column],
               emit_unmatched_probe: bool = False,
               need_build_matched: bool = False,
@@ -297,16 +321,74 @@ def hash_join(build_cols: List[Column], probe_cols: List[Column],
         probe_idx [m] int64,
         build_matched [n_build] bool | None)
     SQL NULL join keys never match (join_row_has_null in kernels.hip).
+    Pairs come in ascending probe row, chain order within a row, on both
+    the fused path (spark.auron.join.fusedProbe.enable) and the legacy one.
     """
     device = probe_cols[0].device
     n_probe = len(probe_cols[0])
     n_build = len(build_cols[0])
     if not _use_native(device):
         return hash_join_ref(build_cols, probe_cols, emit_unmatched_probe, need_build_matched)
-    lib = native.lib()
-    sp = native.stream_ptr(device)
     if table is None:
         table = join_build(build_cols)
+    if len(build_cols) <= JOIN_PROBE_MAX_KEYS and _fused_probe_enabled():
+        return _hash_join_fused(build_cols, probe_cols, emit_unmatched_probe,
+                                need_build_matched, table)
+    return _hash_join_legacy(build_cols, probe_cols, emit_unmatched_probe,
+                             need_build_matched, table)
+
+
+def _hash_join_fused(build_cols, probe_cols, emit_unmatched_probe,
+                     need_build_matched, table):
+    """k_join_probe_count -> cumsum over the per-tile sums -> one .item()
+    for the output size -> k_join_probe_fill. build_matched is set by the
+    count kernel, whose walk visits every match anyway, so the fill
+    kernel's one-match rows touch neither the table nor a key."""
+    device = probe_cols[0].device
+    n_probe = len(probe_cols[0])
+    n_build = len(build_cols[0])
+    lib = native.lib()
+    sp = native.stream_ptr(device)
+    bm = torch.zeros(n_build, dtype=torch.uint8, device=device) if need_build_matched else None
+    if n_probe == 0:
+        empty = torch.empty(0, dtype=torch.int64, device=device)
+        return empty, empty.clone(), (bm.bool() if bm is not None else None)
+    ncols = len(build_cols)
+    descs, keep = _join_key_descs(build_cols, probe_cols)
+    tile = join_probe_tile()
+    n_tiles = (n_probe + tile - 1) // tile
+    counts = torch.empty(n_probe, dtype=torch.int32, device=device)
+    first = torch.empty(n_probe, dtype=torch.int32, device=device)
+    tile_sums = torch.empty(n_tiles, dtype=torch.int64, device=device)
+    emit = 1 if emit_unmatched_probe else 0
+    rc = lib.au_join_probe_count(descs.ctypes.data, ncols, n_probe,
+                                 table.heads.data_ptr(), table.cap,
+                                 table.nxt.data_ptr(), SPARK_SEED, emit,
+                                 counts.data_ptr(), first.data_ptr(),
+                                 tile_sums.data_ptr(),
+                                 bm.data_ptr() if bm is not None and n_build else None,
+                                 sp)
+    native.check(rc, "au_join_probe_count")
+    tile_ends = torch.cumsum(tile_sums, 0)
+    total = int(tile_ends[-1].item())
+    build_idx = torch.empty(max(total, 1), dtype=torch.int64, device=device)
+    probe_idx = torch.empty(max(total, 1), dtype=torch.int64, device=device)
+    rc = lib.au_join_probe_fill(descs.ctypes.data, ncols, n_probe,
+                                table.nxt.data_ptr(), counts.data_ptr(),
+                                first.data_ptr(), tile_ends.data_ptr(), emit,
+                                build_idx.data_ptr(), probe_idx.data_ptr(), sp)
+    native.check(rc, "au_join_probe_fill")
+    del keep
+    return build_idx[:total], probe_idx[:total], (bm.bool() if bm is not None else None)
+
+
+def _hash_join_legacy(build_cols, probe_cols, emit_unmatched_probe,
+                      need_build_matched, table):
+    device = probe_cols[0].device
+    n_probe = len(probe_cols[0])
+    n_build = len(build_cols[0])
+    lib = native.lib()
+    sp = native.stream_ptr(device)
     heads, nxt, cap, bhash = table.heads, table.nxt, table.cap, table.bhash
     phash = murmur3(probe_cols)
     bdescs, bkeep = native.pack_descs(build_cols, device)
@@ -334,6 +416,37 @@ def hash_join(build_cols: List[Column], probe_cols: List[Column],
     native.check(rc, "au_join_fill")
     del bkeep, pkeep
     return build_idx[:total], probe_idx[:total], (bm.bool() if bm is not None else None)
+
+
+def join_exists(build_cols: List[Column], probe_cols: List[Column],
+                table: Optional["JoinTable"] = None) -> torch.Tensor:
+    """Per-probe-row "has at least one match" (semi/anti/existence joins),
+    bool [n_probe]. k_join_exists stops at the first match and reuses a
+    prebuilt `table`; with the fused probe switched off, or more than 8 key
+    columns, it is join_counts(...) > 0."""
+    device = probe_cols[0].device
+    n_probe = len(probe_cols[0])
+    if not _use_native(device):
+        _, pi, _ = hash_join_ref(build_cols, probe_cols, False, False)
+        out = torch.zeros(n_probe, dtype=torch.bool, device=device)
+        if pi.numel():
+            out[pi] = True
+        return out
+    if len(build_cols) > JOIN_PROBE_MAX_KEYS or not _fused_probe_enabled():
+        return join_counts(build_cols, probe_cols) > 0
+    if table is None:
+        table = join_build(build_cols)
+    out = torch.empty(n_probe, dtype=torch.bool, device=device)  # kernel writes 0/1 bytes
+    if n_probe:
+        descs, keep = _join_key_descs(build_cols, probe_cols)
+        rc = native.lib().au_join_exists(descs.ctypes.data, len(build_cols),
+                                         n_probe, table.heads.data_ptr(),
+                                         table.cap, table.nxt.data_ptr(),
+                                         SPARK_SEED, out.data_ptr(),
+                                         native.stream_ptr(device))
+        native.check(rc, "au_join_exists")
+        del keep
+    return out
 
 
 def join_counts(build_cols: List[Column], probe_cols: List[Column]) -> torch.Tensor:
