@@ -107,12 +107,14 @@ class Column:
                 scaled = [int(round(float(v) * (10 ** dtype.scale))) for v in tvals]
                 data = torch.tensor(scaled, dtype=torch.int64)
             elif dtype.code == dtypes.DECIMAL128:
-                from decimal import Decimal
+                from decimal import Context, Decimal
 
                 m64 = (1 << 64) - 1
+                wide = Context(prec=80)  # the default rounds at 28 digits
                 limbs = []
                 for v in tvals:
-                    iv = int(Decimal(str(v)).scaleb(dtype.scale))
+                    iv = int(Decimal(str(v)).scaleb(dtype.scale,
+                                                    context=wide))
                     lo = iv & m64
                     limbs.append(((lo - (1 << 64)) if lo >= (1 << 63) else lo,
                                   iv >> 64))
@@ -361,8 +363,11 @@ class Column:
             p = max(self.dtype.precision, sc + 1, 1)
             return pa.array(vals, type=pa.decimal128(p, sc))
         if self.dtype.code == dtypes.DECIMAL128:
-            from decimal import Decimal
+            from decimal import Context, Decimal
 
+            # scaleb rounds to its context: the default 28 digits would
+            # round a 38-digit value
+            wide = Context(prec=80)
             sc = self.dtype.scale
             lo = c.data[:, 0].numpy()
             hi = c.data[:, 1].numpy()
@@ -372,7 +377,7 @@ class Column:
                     vals.append(None)
                 else:
                     v = (int(hi[i]) << 64) | (int(lo[i]) & ((1 << 64) - 1))
-                    vals.append(Decimal(v).scaleb(-sc))
+                    vals.append(Decimal(v).scaleb(-sc, context=wide))
             p = max(self.dtype.precision, sc + 1, 1)
             return pa.array(vals, type=pa.decimal128(min(p, 38), sc))
         np_arr = c.data.numpy()

@@ -149,6 +149,14 @@ JOIN_FUSED_PROBE = _opt("spark.auron.join.fusedProbe.enable", True, bool,
                         "k_join_count + torch scan + k_join_fill, and "
                         "join_counts for semi/anti/existence joins)",
                         env="AURON_JOIN_FUSED_PROBE")
+DECIMAL128_NATIVE_ARITH = _opt("spark.auron.decimal128.nativeArith.enable",
+                               True, bool,
+                               "run exact decimal128 + - * /, comparisons, "
+                               "casts, abs and CheckOverflow on the "
+                               "k_dec128_* kernels (off: the exact "
+                               "host-integer reference path, also on GPU "
+                               "batches)",
+                               env="AURON_DECIMAL128_NATIVE_ARITH")
 SPILL_DIR = _opt("spark.auron.spill.dir", "", str,
                  "directory for disk-tier spill files (empty = system tmp)",
                  env="AURON_SPILL_DIR")

@@ -136,6 +136,53 @@ def decimal128(precision: int = 38, scale: int = 2) -> DataType:
     return DataType(DECIMAL128, precision, scale)
 
 
+MAX_DECIMAL_PRECISION = 38
+_MIN_ADJUSTED_SCALE = 6
+
+# integer operands of decimal arithmetic count as decimals of scale 0
+_INT_AS_DECIMAL = {INT8: (3, 0), INT16: (5, 0), INT32: (10, 0),
+                   DATE32: (10, 0), INT64: (20, 0)}
+
+
+def decimal_operand(dt: DataType):
+    """(precision, scale) an operand of exact decimal arithmetic counts
+    as, or None when it cannot take part (floats, strings, ...)."""
+    if dt.code in (DECIMAL64, DECIMAL128):
+        return dt.precision, dt.scale
+    return _INT_AS_DECIMAL.get(dt.code)
+
+
+def is_decimal128_op(a: DataType, b: DataType) -> bool:
+    """Operand rule of the exact 128-bit path: at least one DECIMAL128 and
+    the other a DECIMAL128, a DECIMAL64 or an integer type."""
+    return (DECIMAL128 in (a.code, b.code)
+            and decimal_operand(a) is not None
+            and decimal_operand(b) is not None)
+
+
+def decimal_result_type(op: str, a: DataType, b: DataType):
+    """Spark's DecimalPrecision result type of `a op b` for + - * / with
+    allowPrecisionLoss=true, as decimal128(p, s); None when
+    is_decimal128_op does not hold (the operation keeps its other route)."""
+    if op not in ("+", "-", "*", "/") or not is_decimal128_op(a, b):
+        return None
+    (p1, s1), (p2, s2) = decimal_operand(a), decimal_operand(b)
+    if op in "+-":
+        s = max(s1, s2)
+        p = max(p1 - s1, p2 - s2) + s + 1
+    elif op == "*":
+        p, s = p1 + p2 + 1, s1 + s2
+    else:
+        s = max(_MIN_ADJUSTED_SCALE, s1 + p2 + 1)
+        p = p1 - s1 + s2 + s
+    if p > MAX_DECIMAL_PRECISION:
+        int_digits = p - s
+        s = max(MAX_DECIMAL_PRECISION - int_digits,
+                min(s, _MIN_ADJUSTED_SCALE))
+        p = MAX_DECIMAL_PRECISION
+    return decimal128(p, s)
+
+
 def list_of(child: DataType) -> DataType:
     assert child.code != LIST, "nested lists unsupported (round 2)"
     return DataType(LIST, child.code, child.scale)

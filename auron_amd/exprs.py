@@ -207,9 +207,11 @@ class Literal(Expr):
             v = int(round(float(self.value) * 10 ** dt.scale))
             return Column(dt, torch.full((n,), v, dtype=torch.int64, device=device))
         if dt.code == dtypes.DECIMAL128:
-            from decimal import Decimal
+            from decimal import Context, Decimal
 
-            iv = int(Decimal(str(self.value)).scaleb(dt.scale).to_integral_value())
+            wide = Context(prec=80)  # the default rounds at 28 digits
+            iv = int(Decimal(str(self.value)).scaleb(dt.scale, context=wide)
+                     .to_integral_value(context=wide))
             m64 = (1 << 64) - 1
             lo = iv & m64
             if lo >= 1 << 63:
@@ -234,6 +236,8 @@ def _promote(l: Column, r: Column) -> Tuple[Column, Column, DataType]:
     if a.code == b.code and a.code != dtypes.DECIMAL64:
         return l, r, a
     if dtypes.DECIMAL128 in (a.code, b.code):
+        # a float operand, or `%`: Arith and Cmp take the exact decimal128
+        # kernels (dtypes.is_decimal128_op) before they promote
         return (_cast_col(l, dtypes.float64), _cast_col(r, dtypes.float64),
                 dtypes.float64)
     if a.code == dtypes.DECIMAL64 or b.code == dtypes.DECIMAL64:
@@ -253,7 +257,9 @@ _US_PER_SEC = 1_000_000
 
 
 def _cast_col(c: Column, dt: DataType) -> Column:
-    if c.dtype.code == dt.code and c.dtype.scale == dt.scale:
+    if (c.dtype.code == dt.code and c.dtype.scale == dt.scale
+            and not (dt.code == dtypes.DECIMAL128
+                     and dt.precision < c.dtype.precision)):
         return c
     if c.dtype.is_string or dt.is_string:
         return _cast_string(c, dt)
@@ -297,32 +303,100 @@ def dec64_to_dec128(data: torch.Tensor) -> torch.Tensor:
     return torch.stack([data, hi], dim=1)
 
 
+def _dec128_arith(op: str, l: Column, r: Column) -> Column:
+    """Exact decimal128 + - * / under dtypes.is_decimal128_op: Spark's
+    result type, one kernel launch, overflow and x / 0 become null without
+    touching the host."""
+    from . import ops
+
+    out = dtypes.decimal_result_type(op, l.dtype, r.dtype)
+    s1 = dtypes.decimal_operand(l.dtype)[1]
+    s2 = dtypes.decimal_operand(r.dtype)[1]
+    a, b = l.data, r.data
+    if op in "+-":
+        s = max(s1, s2)
+        fn = ops.dec128_add if op == "+" else ops.dec128_sub
+        data, valid = fn(a, b, s - s1, s - s2, s - out.scale, out.precision,
+                         l.validity, r.validity)
+    elif op == "*":
+        data, valid = ops.dec128_mul(a, b, s1 + s2 - out.scale,
+                                     out.precision, l.validity, r.validity)
+    else:
+        data, valid = ops.dec128_div(a, b, out.scale - s1 + s2,
+                                     out.precision, l.validity, r.validity)
+    return Column(out, data, compact_validity(valid))
+
+
+def _dec128_cmp(op: str, l: Column, r: Column) -> Column:
+    from . import ops
+
+    s1 = dtypes.decimal_operand(l.dtype)[1]
+    s2 = dtypes.decimal_operand(r.dtype)[1]
+    s = max(s1, s2)
+    data = ops.dec128_cmp(l.data, r.data, s - s1, s - s2, op)
+    return Column(dtypes.bool_, data, combine_validity(l, r))
+
+
+_INT_CAST_BITS = {dtypes.INT8: 8, dtypes.INT16: 16, dtypes.INT32: 32,
+                  dtypes.INT64: 64}
+
+
 def _cast_decimal128(c: Column, dt: DataType) -> Column:
+    """Casts with a decimal128 on either side. Decimal and integer sources
+    and targets are exact (ops.dec128_rescale: HALF_UP between decimals,
+    toward zero into integers) and a value the target cannot hold becomes
+    null; floats keep the precision-limited float64 route."""
+    from . import ops
+
     if c.dtype.code == dtypes.DECIMAL128:
-        f = dec128_to_float64(c.data, c.dtype.scale)
-        if dt.code == dtypes.DECIMAL128 or dt.code == dtypes.DECIMAL64:
-            # rescale through float64 only when scales differ; same-scale
-            # narrowing checks the value fits the 64-bit backing exactly
-            if dt.scale == c.dtype.scale and dt.code == dtypes.DECIMAL64:
-                lo, hi = c.data[:, 0], c.data[:, 1]
-                fits = hi == (lo >> 63)
-                if not bool(fits.all() if lo.device.type != "cuda" else True):
-                    raise ValueError("decimal128 -> decimal64 overflow")
-                return Column(dt, lo.clone(), c.validity)
-            scaled = torch.round(f * (10.0 ** dt.scale)).to(torch.int64)
-            if dt.code == dtypes.DECIMAL64:
-                return Column(dt, scaled, c.validity)
-            return Column(dt, dec64_to_dec128(scaled), c.validity)
+        if dt.code in (dtypes.DECIMAL128, dtypes.DECIMAL64):
+            narrow = dt.code == dtypes.DECIMAL64
+            data, valid = ops.dec128_rescale(
+                c.data, dt.scale - c.dtype.scale,
+                min(dt.precision, 18) if narrow else dt.precision,
+                c.validity, narrow_out=narrow)
+            return Column(dt, data, compact_validity(valid))
         if dt.is_float:
+            f = dec128_to_float64(c.data, c.dtype.scale)
             return Column(dt, f.to(dt.torch_dtype), c.validity)
         if dt.is_integer:
-            return Column(dt, f.trunc().to(dt.torch_dtype), c.validity)
+            bits = _INT_CAST_BITS[dt.code]
+            data, valid = ops.dec128_rescale(
+                c.data, -c.dtype.scale, None, c.validity,
+                bound=1 << (bits - 1), truncate=True, asym=True,
+                narrow_out=True)
+            return Column(dt, data.to(dt.torch_dtype),
+                          compact_validity(valid))
         raise TypeError(f"cast decimal128 -> {dt}")
     # -> decimal128
-    if c.dtype.code == dtypes.DECIMAL64 and c.dtype.scale == dt.scale:
-        return Column(dt, dec64_to_dec128(c.data), c.validity)
+    src = dtypes.decimal_operand(c.dtype)
+    if src is not None:
+        data, valid = ops.dec128_rescale(c.data, dt.scale - src[1],
+                                         dt.precision, c.validity)
+        return Column(dt, data, compact_validity(valid))
     as64 = _cast_col(c, dtypes.decimal64(18, dt.scale))
     return Column(dt, dec64_to_dec128(as64.data), c.validity)
+
+
+def _parse_decimal128(v: str, dt: DataType):
+    """String -> unscaled integer at dt's scale, HALF_UP; None when the text
+    is no finite number or the value exceeds dt's precision."""
+    import decimal
+
+    try:
+        d = decimal.Decimal(v.strip())
+    except decimal.InvalidOperation:
+        return None
+    if not d.is_finite():
+        return None
+    with decimal.localcontext() as ctx:
+        ctx.prec = 200
+        try:
+            iv = int(d.scaleb(dt.scale).to_integral_value(
+                rounding=decimal.ROUND_HALF_UP))
+        except decimal.InvalidOperation:
+            return None
+    return iv if abs(iv) < 10 ** dt.precision else None
 
 
 def _cast_timestamp(c: Column, dt: DataType) -> Column:
@@ -386,6 +460,18 @@ def _format_ts_micros(us: int) -> str:
     return base
 
 
+def _decimal128_from_ints(ints, dt: DataType, device) -> Column:
+    """Unscaled Python ints (None = null) -> decimal128 column."""
+    m64 = (1 << 64) - 1
+    rows = []
+    for iv in ints:
+        lo = (iv or 0) & m64
+        rows.append([lo - (1 << 64) if lo >> 63 else lo, (iv or 0) >> 64])
+    data = torch.tensor(rows, dtype=torch.int64).reshape(len(rows), 2)
+    valid = torch.tensor([iv is not None for iv in ints], dtype=torch.bool)
+    return Column(dt, data.to(device), compact_validity(valid.to(device)))
+
+
 def _cast_string(c: Column, dt: DataType) -> Column:
     import datetime as _dt_mod
 
@@ -396,6 +482,10 @@ def _cast_string(c: Column, dt: DataType) -> Column:
         # string -> numeric/date: host round-trip (cold path in TPC-DS);
         # unparseable values yield null (try_cast/non-ANSI cast semantics)
         vals = c.to_pylist()
+        if dt.code == dtypes.DECIMAL128:
+            return _decimal128_from_ints(
+                [None if v is None else _parse_decimal128(v, dt)
+                 for v in vals], dt, c.device)
         out = []
         for v in vals:
             if v is None:
@@ -455,6 +545,9 @@ class Arith(Expr):
     def eval(self, batch: RecordBatch) -> Column:
         l = self.left.eval(batch)
         r = self.right.eval(batch)
+        if (self.op in ("+", "-", "*", "/")
+                and dtypes.is_decimal128_op(l.dtype, r.dtype)):
+            return _dec128_arith(self.op, l, r)
         # decimal same-scale fast path for +/-
         if (l.dtype.code == dtypes.DECIMAL64 and r.dtype.code == dtypes.DECIMAL64
                 and l.dtype.scale == r.dtype.scale and self.op in "+-"):
@@ -517,6 +610,8 @@ class Cmp(Expr):
         if l.dtype.is_string or r.dtype.is_string:
             data = strings.compare(l, r, self.op)
             return Column(dtypes.bool_, data, combine_validity(l, r))
+        if dtypes.is_decimal128_op(l.dtype, r.dtype):
+            return _dec128_cmp(self.op, l, r)
         l, r, _ = _promote(l, r)
         a, b = l.data, r.data
         fn = {"==": torch.eq, "!=": torch.ne, "<": torch.lt, "<=": torch.le, ">": torch.gt, ">=": torch.ge}[self.op]
@@ -745,6 +840,13 @@ class Abs(Expr):
 
     def eval(self, batch: RecordBatch) -> Column:
         c = self.child.eval(batch)
+        if c.dtype.code == dtypes.DECIMAL128:
+            from . import ops
+
+            data, valid = ops.dec128_rescale(
+                c.data, 0, dtypes.MAX_DECIMAL_PRECISION, c.validity,
+                abs_=True)
+            return Column(c.dtype, data, compact_validity(valid))
         return Column(c.dtype, torch.abs(c.data), c.validity)
 
 

@@ -1085,13 +1085,21 @@ class UnscaledValue(Expr):
 @dataclass(eq=False)
 class MakeDecimal(Expr):
     """spark_make_decimal: unscaled int64 -> decimal(p,s) (inverse of
-    UnscaledValue; nulls for values whose digits exceed p)."""
+    UnscaledValue; nulls for values whose digits exceed p). p > 18 yields
+    decimal128."""
     child: Expr
     precision: int = 18
     scale: int = 2
 
     def eval(self, batch):
         c = self.child.eval(batch)
+        if self.precision > 18:
+            from . import ops
+
+            data, valid = ops.dec128_rescale(c.data.to(torch.int64), 0,
+                                             self.precision, c.validity)
+            return Column(dtypes.decimal128(self.precision, self.scale),
+                          data, compact_validity(valid))
         data = c.data.to(torch.int64)
         limit = 10 ** min(self.precision, 18)
         ok = (data > -limit) & (data < limit)
@@ -1118,6 +1126,13 @@ class CheckOverflow(Expr):
             v = ok if v is None else (v & ok)
             return Column(dtypes.decimal64(self.precision, c.dtype.scale),
                           c.data, compact_validity(v))
+        if c.dtype.code == dtypes.DECIMAL128:
+            from . import ops
+
+            data, valid = ops.dec128_rescale(c.data, 0, self.precision,
+                                             c.validity)
+            return Column(dtypes.decimal128(self.precision, c.dtype.scale),
+                          data, compact_validity(valid))
         return c
 
 

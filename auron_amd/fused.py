@@ -127,7 +127,15 @@ class _Compiler:
         self.op(PUSH_LIT_I, 0, int(v), d=1)
 
     def typeof(self, e) -> DataType:
-        """Result dtype, mirroring each eval()'s promotion logic."""
+        """Result dtype, mirroring each eval()'s promotion logic. Any tree
+        that touches DECIMAL128 is refused: the interpreter's slots are 64
+        bits wide, and exact 128-bit arithmetic has kernels of its own."""
+        dt = self._typeof(e)
+        if dt.code == dtypes.DECIMAL128:
+            raise _Unsupported("decimal128")
+        return dt
+
+    def _typeof(self, e) -> DataType:
         if isinstance(e, Col):
             dt = self.schema.get(e.name)
             if dt is None:
@@ -256,6 +264,7 @@ class _Compiler:
                 self.lit_i(int(e.value))
             return dt
         if isinstance(e, (Cast, TryCast)):
+            self.typeof(e)  # refuses a DECIMAL128 target
             frm = self.emit(e.child)
             self.coerce(frm, e.to)
             return e.to

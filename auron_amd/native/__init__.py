@@ -132,6 +132,20 @@ def _try_load():
               "au_prefix_sum_i128", "au_window_frame_sum_i128",
               "au_window_frame_minmax_i128"):
         getattr(lib, f).restype = ctypes.c_int
+    ci = ctypes.c_int
+    u64 = ctypes.c_uint64
+    lib.au_dec128_grid_threads.argtypes = []
+    lib.au_dec128_grid_threads.restype = i64
+    lib.au_dec128_addsub.argtypes = [c, ci, c, c, ci, c, i64, ci, ci, ci, ci,
+                                     ci, c, c, c]
+    lib.au_dec128_mul.argtypes = [c, ci, c, c, ci, c, i64, ci, ci, c, c, c]
+    lib.au_dec128_div.argtypes = [c, ci, c, c, ci, c, i64, ci, ci, c, c, c]
+    lib.au_dec128_cmp.argtypes = [c, ci, c, ci, i64, ci, ci, ci, c, c]
+    lib.au_dec128_rescale.argtypes = [c, ci, c, i64, ci, ci, u64, u64, c, ci,
+                                      c, c]
+    for f in ("au_dec128_addsub", "au_dec128_mul", "au_dec128_div",
+              "au_dec128_cmp", "au_dec128_rescale"):
+        getattr(lib, f).restype = ctypes.c_int
     for f in ("au_murmur3", "au_group_ids", "au_join_build", "au_join_count",
               "au_join_fill", "au_pmod", "au_part_hist", "au_part_scatter"):
         getattr(lib, f).restype = ctypes.c_int

@@ -16,7 +16,8 @@ SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "parquet.hip"),
            os.path.join(CSRC, "agg.hip"),
            os.path.join(CSRC, "fused.hip"),
            os.path.join(CSRC, "rangepart.hip"),
-           os.path.join(CSRC, "window.hip")]
+           os.path.join(CSRC, "window.hip"),
+           os.path.join(CSRC, "dec128.hip")]
 HIPCC = os.environ.get("HIPCC", "hipcc")
 ARCH = os.environ.get("AURON_OFFLOAD_ARCH", "gfx950")
 

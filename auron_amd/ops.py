@@ -1019,6 +1019,326 @@ def window_frame_minmax_i128(x: torch.Tensor, a: torch.Tensor,
     return out
 
 
+# ------------------------------------------------ exact decimal128 arithmetic
+# An operand is either int64 [n,2] limbs or an integer [n] tensor (decimal64
+# or integer backing), read as a sign-extended 128-bit integer. Every op
+# builds an exact wide intermediate, divides by a power of ten (or by b)
+# rounding HALF_UP on the magnitude, and clears the row's validity when the
+# result's magnitude reaches 10^p. The *_ref twins do the same in Python
+# integers on the host: they are the CPU execution path and the oracle for
+# the k_dec128_* kernels, and accept tensors on any device.
+DEC128_MAX_POW10 = 38  # the kernels' powers of ten; more takes the reference
+DEC128_CMP_OPS = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5}
+_DX_ABS, _DX_NEGATE, _DX_TRUNCATE, _DX_ASYM = 1, 2, 4, 8
+
+
+def dec128_grid_threads() -> int:
+    """Threads of the k_dec128_* kernels' largest grid; one more row wraps
+    the grid-stride loop."""
+    return int(native.lib().au_dec128_grid_threads())
+
+
+def _dec128_native(device: torch.device, *powers: int) -> bool:
+    if any(k > DEC128_MAX_POW10 for k in powers):
+        return False
+    if not _use_native(device):
+        return False
+    from .config import DECIMAL128_NATIVE_ARITH, AuronConf
+
+    return bool(AuronConf().get(DECIMAL128_NATIVE_ARITH))
+
+
+def _dec128_operand_args(x: torch.Tensor):
+    if x.dim() == 2:
+        _i128_args(x)
+    else:
+        assert x.dim() == 1 and x.dtype in (
+            torch.int8, torch.int16, torch.int32, torch.int64), \
+            f"expected int64 [n,2] limbs or integer [n], got {x.dtype} " \
+            f"{tuple(x.shape)}"
+
+
+def _dec128_pair_args(a, b, va, vb, *powers):
+    _dec128_operand_args(a)
+    _dec128_operand_args(b)
+    assert a.shape[0] == b.shape[0], (tuple(a.shape), tuple(b.shape))
+    for v in (va, vb):
+        assert v is None or (v.dtype == torch.bool
+                             and v.numel() == a.shape[0])
+    assert all(k >= 0 for k in powers), powers
+
+
+def _dec128_ints(x: torch.Tensor):
+    """Rows as a numpy object array of Python ints."""
+    import numpy as np
+
+    h = x.detach().cpu().numpy()
+    if h.ndim == 2:
+        lo = h[:, 0].astype(np.uint64).astype(object)
+        return h[:, 1].astype(object) * (1 << 64) + lo
+    return h.astype(np.int64).astype(object)
+
+
+def _dec128_valid(n, *vs):
+    import numpy as np
+
+    ok = np.ones(n, dtype=bool)
+    for v in vs:
+        if v is not None:
+            ok &= v.detach().cpu().numpy()
+    return ok
+
+
+def _div_half_up(x: int, d: int, truncate: bool = False) -> int:
+    q, r = divmod(abs(x), d)
+    if not truncate and 2 * r >= d:
+        q += 1
+    return -q if x < 0 else q
+
+
+def _dec128_pack(vals, ok, bound, device, narrow=False, asym=False):
+    """(data, valid) tensors from Python ints: a row is kept when its input
+    validity holds, its value is not None and |value| < bound (`asym` also
+    keeps -bound); other rows store zero."""
+    import numpy as np
+
+    n = len(vals)
+    lo = np.zeros(n, dtype=np.uint64)
+    hi = np.zeros(n, dtype=np.int64)
+    valid = np.zeros(n, dtype=bool)
+    m64 = (1 << 64) - 1
+    for i, v in enumerate(vals):
+        if not ok[i] or v is None:
+            continue
+        if not (-bound < v < bound or (asym and v == -bound)):
+            continue
+        valid[i] = True
+        lo[i] = v & m64
+        hi[i] = v >> 64
+    lo = lo.view(np.int64)
+    data = lo if narrow else np.stack([lo, hi], axis=1)
+    return (torch.from_numpy(np.ascontiguousarray(data)).to(device),
+            torch.from_numpy(valid).to(device))
+
+
+def _dec128_addsub_ref(a, b, ka, kb, d, p, va, vb, sub):
+    _dec128_pair_args(a, b, va, vb, ka, kb, d)
+    sign = -1 if sub else 1
+    pa, pb, pd = 10 ** ka, 10 ** kb, 10 ** d
+    vals = [_div_half_up(x * pa + sign * y * pb, pd)
+            for x, y in zip(_dec128_ints(a), _dec128_ints(b))]
+    return _dec128_pack(vals, _dec128_valid(a.shape[0], va, vb), 10 ** p,
+                        a.device)
+
+
+def dec128_add_ref(a, b, ka, kb, d, p, va=None, vb=None):
+    """Oracle for dec128_add (Python integers on the host)."""
+    return _dec128_addsub_ref(a, b, ka, kb, d, p, va, vb, False)
+
+
+def dec128_sub_ref(a, b, ka, kb, d, p, va=None, vb=None):
+    """Oracle for dec128_sub (Python integers on the host)."""
+    return _dec128_addsub_ref(a, b, ka, kb, d, p, va, vb, True)
+
+
+def dec128_mul_ref(a, b, d, p, va=None, vb=None):
+    """Oracle for dec128_mul (Python integers on the host)."""
+    _dec128_pair_args(a, b, va, vb, d)
+    pd = 10 ** d
+    vals = [_div_half_up(x * y, pd)
+            for x, y in zip(_dec128_ints(a), _dec128_ints(b))]
+    return _dec128_pack(vals, _dec128_valid(a.shape[0], va, vb), 10 ** p,
+                        a.device)
+
+
+def dec128_div_ref(a, b, k, p, va=None, vb=None):
+    """Oracle for dec128_div (Python integers on the host)."""
+    _dec128_pair_args(a, b, va, vb, k)
+    pk = 10 ** k
+
+    def one(x, y):
+        if y == 0:
+            return None
+        q = _div_half_up(x * pk, abs(y))
+        return -q if y < 0 else q
+
+    vals = [one(x, y) for x, y in zip(_dec128_ints(a), _dec128_ints(b))]
+    return _dec128_pack(vals, _dec128_valid(a.shape[0], va, vb), 10 ** p,
+                        a.device)
+
+
+def dec128_cmp_ref(a, b, ka, kb, op):
+    """Oracle for dec128_cmp (Python integers on the host)."""
+    import operator
+
+    _dec128_pair_args(a, b, None, None, ka, kb)
+    fn = {"==": operator.eq, "!=": operator.ne, "<": operator.lt,
+          "<=": operator.le, ">": operator.gt, ">=": operator.ge}[op]
+    pa, pb = 10 ** ka, 10 ** kb
+    out = [fn(x * pa, y * pb)
+           for x, y in zip(_dec128_ints(a), _dec128_ints(b))]
+    return torch.tensor(out, dtype=torch.bool).to(a.device)
+
+
+def _dec128_rescale_bound(p, bound, narrow_out):
+    assert (p is None) != (bound is None), "give exactly one of p / bound"
+    if bound is None:
+        bound = 10 ** p
+    assert 0 < bound < (1 << 127)
+    assert not narrow_out or bound <= (1 << 63)
+    return bound
+
+
+def dec128_rescale_ref(x, k, p=None, vx=None, *, bound=None, abs_=False,
+                       negate=False, truncate=False, asym=False,
+                       narrow_out=False):
+    """Oracle for dec128_rescale (Python integers on the host)."""
+    _dec128_operand_args(x)
+    bound = _dec128_rescale_bound(p, bound, narrow_out)
+    pk = 10 ** abs(k)
+
+    def one(v):
+        if abs_:
+            v = abs(v)
+        if negate:
+            v = -v
+        return v * pk if k >= 0 else _div_half_up(v, pk, truncate)
+
+    vals = [one(v) for v in _dec128_ints(x)]
+    return _dec128_pack(vals, _dec128_valid(x.shape[0], vx), bound, x.device,
+                        narrow=narrow_out, asym=asym)
+
+
+def _dec128_operand(x: torch.Tensor):
+    """(tensor, narrow flag) in the form the kernels load."""
+    if x.dim() == 2:
+        return _i128_aligned(x), 0
+    return x.to(torch.int64).contiguous(), 1
+
+
+def _dec128_vptr(v, keep):
+    if v is None:
+        return None
+    v = v.contiguous()
+    keep.append(v)
+    return v.data_ptr()
+
+
+def _dec128_binary(fn, what, a, b, va, vb, ints):
+    lib = native.lib()
+    device = a.device
+    n = a.shape[0]
+    out = torch.empty((n, 2), dtype=torch.int64, device=device)
+    valid = torch.empty(n, dtype=torch.bool, device=device)
+    if n == 0:
+        return out, valid
+    keep = []
+    a, an = _dec128_operand(a)
+    b, bn = _dec128_operand(b)
+    rc = getattr(lib, fn)(a.data_ptr(), an, _dec128_vptr(va, keep),
+                          b.data_ptr(), bn, _dec128_vptr(vb, keep), n, *ints,
+                          out.data_ptr(), valid.data_ptr(),
+                          native.stream_ptr(device))
+    native.check(rc, what)
+    return out, valid
+
+
+def dec128_add(a, b, ka, kb, d, p, va=None, vb=None):
+    """(a*10^ka + b*10^kb) / 10^d rounded HALF_UP -> ([n,2] limbs, valid).
+    valid = va & vb & (|result| < 10^p); a row that is not valid stores
+    zero. One kernel launch, no host sync."""
+    _dec128_pair_args(a, b, va, vb, ka, kb, d)
+    if not _dec128_native(a.device, ka, kb, d, p):
+        return dec128_add_ref(a, b, ka, kb, d, p, va, vb)
+    return _dec128_binary("au_dec128_addsub", "au_dec128_addsub", a, b, va,
+                          vb, (ka, kb, d, p, 0))
+
+
+def dec128_sub(a, b, ka, kb, d, p, va=None, vb=None):
+    """(a*10^ka - b*10^kb) / 10^d, otherwise as dec128_add."""
+    _dec128_pair_args(a, b, va, vb, ka, kb, d)
+    if not _dec128_native(a.device, ka, kb, d, p):
+        return dec128_sub_ref(a, b, ka, kb, d, p, va, vb)
+    return _dec128_binary("au_dec128_addsub", "au_dec128_addsub", a, b, va,
+                          vb, (ka, kb, d, p, 1))
+
+
+def dec128_mul(a, b, d, p, va=None, vb=None):
+    """(a*b) / 10^d rounded HALF_UP over the exact 256-bit product,
+    otherwise as dec128_add."""
+    _dec128_pair_args(a, b, va, vb, d)
+    if not _dec128_native(a.device, d, p):
+        return dec128_mul_ref(a, b, d, p, va, vb)
+    return _dec128_binary("au_dec128_mul", "au_dec128_mul", a, b, va, vb,
+                          (d, p))
+
+
+def dec128_div(a, b, k, p, va=None, vb=None):
+    """round_half_up(a*10^k / b); a zero divisor clears the row's validity.
+    Otherwise as dec128_add."""
+    _dec128_pair_args(a, b, va, vb, k)
+    if not _dec128_native(a.device, k, p):
+        return dec128_div_ref(a, b, k, p, va, vb)
+    return _dec128_binary("au_dec128_div", "au_dec128_div", a, b, va, vb,
+                          (k, p))
+
+
+def dec128_cmp(a, b, ka, kb, op):
+    """a*10^ka <op> b*10^kb -> bool [n], both sides aligned in 256 bits so
+    a 38-digit value times 10^k cannot wrap."""
+    _dec128_pair_args(a, b, None, None, ka, kb)
+    assert op in DEC128_CMP_OPS, op
+    device = a.device
+    if not _dec128_native(device, ka, kb):
+        return dec128_cmp_ref(a, b, ka, kb, op)
+    n = a.shape[0]
+    out = torch.empty(n, dtype=torch.bool, device=device)
+    if n == 0:
+        return out
+    a, an = _dec128_operand(a)
+    b, bn = _dec128_operand(b)
+    rc = native.lib().au_dec128_cmp(a.data_ptr(), an, b.data_ptr(), bn, n, ka,
+                                    kb, DEC128_CMP_OPS[op], out.data_ptr(),
+                                    native.stream_ptr(device))
+    native.check(rc, "au_dec128_cmp")
+    return out
+
+
+def dec128_rescale(x, k, p=None, vx=None, *, bound=None, abs_=False,
+                   negate=False, truncate=False, asym=False,
+                   narrow_out=False):
+    """x*10^k for k >= 0, x/10^-k for k < 0 (HALF_UP, or toward zero with
+    `truncate`), after `abs_` / `negate` -> (data, valid). valid = vx &
+    (|result| < bound), bound = 10^p unless given; `asym` also keeps -bound
+    (two's-complement integer ranges). data is [n,2] limbs, or int64 [n]
+    with `narrow_out` (bound <= 2^63). Serves casts, CheckOverflow, abs."""
+    _dec128_operand_args(x)
+    assert vx is None or (vx.dtype == torch.bool
+                          and vx.numel() == x.shape[0])
+    bound = _dec128_rescale_bound(p, bound, narrow_out)
+    device = x.device
+    if not _dec128_native(device, abs(k)):
+        return dec128_rescale_ref(x, k, None, vx, bound=bound, abs_=abs_,
+                                  negate=negate, truncate=truncate,
+                                  asym=asym, narrow_out=narrow_out)
+    n = x.shape[0]
+    out = torch.empty(n if narrow_out else (n, 2), dtype=torch.int64,
+                      device=device)
+    valid = torch.empty(n, dtype=torch.bool, device=device)
+    if n == 0:
+        return out, valid
+    keep = []
+    x, xn = _dec128_operand(x)
+    flags = (_DX_ABS * abs_ | _DX_NEGATE * negate | _DX_TRUNCATE * truncate
+             | _DX_ASYM * asym)
+    rc = native.lib().au_dec128_rescale(
+        x.data_ptr(), xn, _dec128_vptr(vx, keep), n, k, flags,
+        bound & ((1 << 64) - 1), bound >> 64, out.data_ptr(),
+        int(narrow_out), valid.data_ptr(), native.stream_ptr(device))
+    native.check(rc, "au_dec128_rescale")
+    return out, valid
+
+
 # ================================================================ partition
 def _normalize_hash_col(c: Column) -> Column:
     """Promote key columns to a canonical width before hashing: murmur3

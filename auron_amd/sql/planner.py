@@ -337,6 +337,9 @@ def infer_dtype(e: Expr, types: Dict[str, DataType]) -> Optional[DataType]:
             return lt or rt
         if dtypes.FLOAT64 in (lt.code, rt.code) or dtypes.FLOAT32 in (lt.code, rt.code):
             return dtypes.float64
+        dec128 = dtypes.decimal_result_type(e.op, lt, rt)
+        if dec128 is not None:
+            return dec128
         if lt.code == dtypes.DECIMAL64 or rt.code == dtypes.DECIMAL64:
             if e.op in ("/",):
                 return dtypes.float64
@@ -1563,7 +1566,10 @@ class Planner:
 
             m = _re.match(r"decimal\((\d+),(\d+)\)", tn)
             p, s = (int(m.group(1)), int(m.group(2))) if m else (18, 2)
-            return Cast(e, dtypes.decimal64(min(p, 18), s))
+            if p > 18:
+                return Cast(e, dtypes.decimal128(
+                    min(p, dtypes.MAX_DECIMAL_PRECISION), s))
+            return Cast(e, dtypes.decimal64(p, s))
         if tn in ("int", "integer"):
             return Cast(e, dtypes.int32)
         if tn in ("bigint", "long"):
