@@ -82,15 +82,58 @@ _SPLITTABLE_AGGS = frozenset(
      "first", "first_ignores_null"})
 
 
+# integer key widths as decimal(p, 0) against a decimal128 key
+_INT_KEY_DIGITS = {dtypes.INT8: 3, dtypes.INT16: 5, dtypes.INT32: 10,
+                   dtypes.INT64: 19}
+
+
+def _decimal_key_operand(dt):
+    if dt.code in (dtypes.DECIMAL64, dtypes.DECIMAL128):
+        return dt.precision, dt.scale
+    p = _INT_KEY_DIGITS.get(dt.code)
+    return None if p is None else (p, 0)
+
+
+def _decimal128_key_type(a, b):
+    """Spark's common decimal type of a join key pair with a decimal128 on
+    at least one side and a decimal128, decimal64 or integer on the other,
+    when the two differ in dtype code or scale: scale = max(s1, s2),
+    integer digits = max(p1 - s1, p2 - s2). None for every other pair, and
+    when that type needs more than 38 digits."""
+    if dtypes.DECIMAL128 not in (a.code, b.code):
+        return None
+    if a.code == b.code and a.scale == b.scale:
+        return None  # equal values already have equal limbs
+    oa, ob = _decimal_key_operand(a), _decimal_key_operand(b)
+    if oa is None or ob is None:
+        return None
+    (p1, s1), (p2, s2) = oa, ob
+    s = max(s1, s2)
+    digits = max(p1 - s1, p2 - s2)
+    if s + digits > dtypes.MAX_DECIMAL_PRECISION:
+        return None
+    return dtypes.decimal128(s + digits, s)
+
+
 def _normalize_join_keys(lkeys, rkeys):
     """Promote corresponding key pairs to one dtype: the native kernels
     hash and compare by the build side's dtype, so int32-vs-int64 pairs
-    would silently mismatch (and murmur3 differs between widths)."""
-    from ..exprs import _promote
+    would silently mismatch (and murmur3 differs between widths). A pair
+    with a decimal128 side is cast exactly to the common decimal128 type
+    (raw limbs at different scales are not comparable); only when that
+    type would not fit 38 digits does it take the float64 route."""
+    from ..exprs import _cast_col, _promote
 
     lo, ro = [], []
     for l, r in zip(lkeys, rkeys):
-        if l.dtype.code != r.dtype.code:
+        common = _decimal128_key_type(l.dtype, r.dtype)
+        if common is not None:
+            l, r = _cast_col(l, common), _cast_col(r, common)
+        elif (l.dtype.code == r.dtype.code == dtypes.DECIMAL128
+              and l.dtype.scale != r.dtype.scale):
+            l = _cast_col(l, dtypes.float64)
+            r = _cast_col(r, dtypes.float64)
+        elif l.dtype.code != r.dtype.code:
             l, r, _ = _promote(l, r)
         lo.append(l)
         ro.append(r)

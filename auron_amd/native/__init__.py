@@ -199,6 +199,10 @@ def pack_descs_host(cols) -> Tuple[np.ndarray, list]:
         data = col.data
         if not data.is_contiguous():
             data = data.contiguous()
+        if col.dtype.code == 12 and data.data_ptr() % 16:  # dtypes.DECIMAL128
+            # the kernels load a limb pair in one 16-byte access
+            raise ValueError("decimal128 key column is not 16-byte aligned "
+                             "(ops._key_cols aligns it)")
         keep.append(data)
         arr[i]["data"] = data.data_ptr()
         if col.offsets is not None:

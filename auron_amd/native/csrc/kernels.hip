@@ -34,6 +34,7 @@ enum AuDType : int32_t {
   AU_DECIMAL64 = 9,
   AU_LIST = 10,
   AU_TIMESTAMP = 11,  // int64 microseconds since epoch
+  AU_DECIMAL128 = 12, // [n,2] int64 per row: low 64 bits, signed high limb
 };
 
 struct AuColDesc {
@@ -101,6 +102,42 @@ __device__ uint32_t hash_bytes(const uint8_t* p, int32_t len, uint32_t seed) {
   return fmix(h1, (uint32_t)len);
 }
 
+// Spark hashes a decimal of precision > 18 as
+// hashUnsafeBytes(BigInteger.toByteArray(unscaled)): the minimal big-endian
+// two's-complement bytes, bitLength/8 + 1 of them (1..16). Same mixing as
+// hash_bytes, with the bytes shifted out of the two limbs: the value is
+// moved up so that its first byte is the top byte of the 128 bits, a whole
+// word is then the byte-swapped top 32 bits, a tail byte the top 8.
+__device__ __forceinline__ uint32_t hash_dec128(uint64_t lo, int64_t hi,
+                                                uint32_t seed) {
+  const uint64_t sign = (uint64_t)(hi >> 63);  // 0 or all ones
+  const uint64_t xh = (uint64_t)hi ^ sign, xl = lo ^ sign;
+  const int lz = xh ? __clzll((long long)xh)
+                    : 64 + (xl ? __clzll((long long)xl) : 64);
+  const int len = ((128 - lz) >> 3) + 1;  // bitLength / 8 + 1
+  const int sh = 8 * (16 - len);          // 0, 8, .. 120
+  uint64_t th = (uint64_t)hi, tl = lo;
+  if (sh >= 64) {
+    th = lo << (sh - 64);
+    tl = 0;
+  } else if (sh > 0) {
+    th = (th << sh) | (lo >> (64 - sh));
+    tl = lo << sh;
+  }
+  uint32_t h1 = seed;
+  for (int w = len >> 2; w > 0; w--) {
+    h1 = mixH1(h1, mixK1(__builtin_bswap32((uint32_t)(th >> 32))));
+    th = (th << 32) | (tl >> 32);
+    tl <<= 32;
+  }
+  for (int t = len & 3; t > 0; t--) {
+    // Spark sign-extends each tail byte to int
+    h1 = mixH1(h1, mixK1((uint32_t)(int32_t)(int8_t)(th >> 56)));
+    th <<= 8;
+  }
+  return fmix(h1, (uint32_t)len);
+}
+
 __device__ __forceinline__ bool row_valid(const AuColDesc& c, int64_t i) {
   return c.validity == nullptr || c.validity[i] != 0;
 }
@@ -134,6 +171,11 @@ __device__ uint32_t hash_one(const AuColDesc& c, int64_t i, uint32_t seed) {
       int64_t s = c.offsets[i];
       int64_t e = c.offsets[i + 1];
       return hash_bytes((const uint8_t*)c.data + s, (int32_t)(e - s), seed);
+    }
+    case AU_DECIMAL128: {
+      // one 16-byte load; the host keeps these columns 16-byte aligned
+      const ulonglong2 v = ((const ulonglong2*)c.data)[i];
+      return hash_dec128(v.x, (int64_t)v.y, seed);
     }
   }
   return seed;
@@ -210,6 +252,13 @@ __device__ bool keys_equal(const AuColDesc* a_cols, int64_t ai,
         }
         for (; k < len; k++)
           if (ap[k] != bp[k]) return false;
+        break;
+      }
+      case AU_DECIMAL128: {
+        // exact: the two's-complement value has one representation
+        const ulonglong2 va = ((const ulonglong2*)a.data)[ai];
+        const ulonglong2 vb = ((const ulonglong2*)b.data)[bi];
+        if (va.x != vb.x || va.y != vb.y) return false;
         break;
       }
     }

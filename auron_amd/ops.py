@@ -19,6 +19,7 @@ from .column import Column
 
 SPARK_SEED = 42
 _M32 = 0xFFFFFFFF
+_M64 = (1 << 64) - 1
 
 
 def _use_native(device: torch.device) -> bool:
@@ -71,11 +72,60 @@ def _hash_long_t(v, seed):
     return _fmix(h, 8)
 
 
+def _hash_padded_bytes_t(padded, lens, maxlen, h):
+    """hashUnsafeBytes over rows of a padded byte matrix: `padded` [n, >=
+    maxlen] int64 byte values, `lens` [n] byte counts (<= maxlen), `h` [n]
+    running seeds. Whole words little-endian, tail bytes sign-extended."""
+    hv = h.clone()
+    nwords = maxlen // 4
+    for j in range(nwords):
+        w = (padded[:, 4 * j] | (padded[:, 4 * j + 1] << 8)
+             | (padded[:, 4 * j + 2] << 16) | (padded[:, 4 * j + 3] << 24))
+        m = lens >= 4 * (j + 1)
+        hv = torch.where(m, _mixh1(hv, _mixk1(w)), hv)
+    aligned = lens & ~3
+    for t in range(maxlen):
+        m = (t >= aligned) & (t < lens)
+        if not bool(m.any()):
+            continue
+        b = padded[:, t]
+        sb = torch.where(b >= 128, (b - 256) & _M32, b)
+        hv = torch.where(m, _mixh1(hv, _mixk1(sb)), hv)
+    return _fmix(hv, lens & _M32)
+
+
+def _hash_dec128_t(d, h):
+    """Spark's hash of a decimal with precision > 18 over [n,2] limbs:
+    hashUnsafeBytes(BigInteger.toByteArray(unscaled)). toByteArray is the
+    minimal big-endian two's-complement encoding: the 16 bytes of the value
+    less every leading byte that only repeats the sign (a byte equal to the
+    sign byte whose successor's top bit is the sign bit too)."""
+    lo, hi = d[:, 0], d[:, 1]
+    shifts = range(56, -8, -8)
+    B = torch.stack([(hi >> s) & 0xFF for s in shifts]
+                    + [(lo >> s) & 0xFF for s in shifts], dim=1)  # big-endian
+    sign = (hi >> 63) & 1
+    redundant = ((B[:, :15] == (sign * 0xFF)[:, None])
+                 & ((B[:, 1:] >> 7) == sign[:, None]))
+    skip = torch.cumprod(redundant.to(torch.int64), dim=1).sum(dim=1)
+    lens = 16 - skip
+    idx = skip[:, None] + torch.arange(16, device=d.device)[None, :]
+    return _hash_padded_bytes_t(B.gather(1, idx.clamp(max=15)), lens, 16, h)
+
+
+def _spark_narrow_decimal(dt) -> bool:
+    """A DECIMAL128-coded type that Spark hashes as a long: precision <= 18,
+    so the value is its low limb."""
+    return dt.code == dtypes.DECIMAL128 and dt.precision <= 18
+
+
 def murmur3_ref(cols: List[Column], seed: int = SPARK_SEED) -> torch.Tensor:
     """Pure-torch Spark Murmur3_x86_32, bit-exact vs the HIP kernel.
 
     Reference semantics: spark_hash.rs (seed-chained per column, nulls
-    skipped, -0.0 normalized, strings hashed as UTF-8 bytes).
+    skipped, -0.0 normalized, strings hashed as UTF-8 bytes, decimals by
+    precision: <= 18 as the unscaled long, wider as the minimal big-endian
+    bytes of the unscaled value).
     """
     n = len(cols[0])
     device = cols[0].device
@@ -87,22 +137,7 @@ def murmur3_ref(cols: List[Column], seed: int = SPARK_SEED) -> torch.Tensor:
             lens = S.lengths(c)
             maxlen = int(lens.max().item()) if n else 0
             padded = S.to_padded(c, max(maxlen, 1)).to(torch.int64)
-            hv = h.clone()
-            nwords = maxlen // 4
-            for j in range(nwords):
-                w = (padded[:, 4 * j] | (padded[:, 4 * j + 1] << 8)
-                     | (padded[:, 4 * j + 2] << 16) | (padded[:, 4 * j + 3] << 24))
-                m = lens >= 4 * (j + 1)
-                hv = torch.where(m, _mixh1(hv, _mixk1(w)), hv)
-            aligned = lens & ~3
-            for t in range(maxlen):
-                m = (t >= aligned) & (t < lens)
-                if not bool(m.any()):
-                    continue
-                b = padded[:, t]
-                sb = torch.where(b >= 128, (b - 256) & _M32, b)
-                hv = torch.where(m, _mixh1(hv, _mixk1(sb)), hv)
-            hv = _fmix(hv, lens & _M32)
+            hv = _hash_padded_bytes_t(padded, lens, maxlen, h)
         else:
             d = c.data
             code = c.dtype.code
@@ -123,6 +158,11 @@ def murmur3_ref(cols: List[Column], seed: int = SPARK_SEED) -> torch.Tensor:
                 f = torch.where(d == 0, torch.zeros_like(d), d)
                 v = f.view(torch.int64)
                 hv = _hash_long_t(v, h)
+            elif code == dtypes.DECIMAL128:
+                if _spark_narrow_decimal(c.dtype):
+                    hv = _hash_long_t(d[:, 0], h)
+                else:
+                    hv = _hash_dec128_t(d, h)
             else:
                 raise TypeError(c.dtype.name)
         if c.validity is not None:
@@ -134,19 +174,62 @@ def murmur3_ref(cols: List[Column], seed: int = SPARK_SEED) -> torch.Tensor:
     return h.to(torch.int32)
 
 
-def murmur3(cols: List[Column], seed: int = SPARK_SEED) -> torch.Tensor:
+def _key_cols(cols: List[Column]) -> List[Column]:
+    """Key columns as the native kernels read them: a decimal128 column's
+    limb pairs contiguous and 16-byte aligned (hash_one and keys_equal load
+    a pair in one 16-byte access)."""
+    out = []
+    for c in cols:
+        if c.dtype.code == dtypes.DECIMAL128:
+            d = _i128_aligned(c.data)
+            if d is not c.data:
+                c = Column(c.dtype, d, c.validity)
+        out.append(c)
+    return out
+
+
+def _spark_hash_cols(cols: List[Column]) -> List[Column]:
+    """Columns as Spark's row hash sees them. AuColDesc carries no
+    precision, so a DECIMAL128-coded column of precision <= 18 (hashed by
+    Spark as a long) goes to the kernel as a DECIMAL64 over its low limb."""
+    out = []
+    for c in cols:
+        if _spark_narrow_decimal(c.dtype):
+            c = Column(dtypes.decimal64(c.dtype.precision, c.dtype.scale),
+                       c.data[:, 0].contiguous(), c.validity)
+        out.append(c)
+    return out
+
+
+def _murmur3_native(cols: List[Column], seed: int = SPARK_SEED) -> torch.Tensor:
+    """k_murmur3 over the columns as they are: every DECIMAL128 column by
+    the byte rule, whatever its precision."""
     device = cols[0].device
     n = len(cols[0])
-    if not _use_native(device):
-        return murmur3_ref(cols, seed)
     lib = native.lib()
     out = torch.empty(n, dtype=torch.int32, device=device)
-    descs, keep = native.pack_descs(cols, device)
+    descs, keep = native.pack_descs(_key_cols(cols), device)
     rc = lib.au_murmur3(descs.data_ptr(), len(cols), n, seed, out.data_ptr(),
                         native.stream_ptr(device))
     native.check(rc, "au_murmur3")
     del keep
     return out
+
+
+def murmur3(cols: List[Column], seed: int = SPARK_SEED) -> torch.Tensor:
+    device = cols[0].device
+    if not _use_native(device):
+        return murmur3_ref(cols, seed)
+    return _murmur3_native(_spark_hash_cols(cols), seed)
+
+
+def _join_hash(cols: List[Column]) -> torch.Tensor:
+    """Row hash of a join table. The fused probe kernels hash the probe key
+    in-kernel from the same descriptors they compare with, so build and
+    probe rows take the kernel's rule for the column's dtype code alone
+    (a decimal128 key by its bytes at every precision). The table is
+    internal: only the two sides have to agree."""
+    return _murmur3_native(cols)
 
 
 # ================================================================= group-by
@@ -162,6 +245,17 @@ def _key_tuple_lists(cols: List[Column]):
 
     lists = []
     for c in cols:
+        if c.dtype.code == dtypes.DECIMAL128:
+            # exact unscaled ints: to_pylist divides into a float, which
+            # merges neighbouring wide values
+            d = c.data.to("cpu")
+            valid = None if c.validity is None else c.validity.tolist()
+            vals = [(h << 64) | (l & _M64) for l, h in
+                    zip(d[:, 0].tolist(), d[:, 1].tolist())]
+            if valid is not None:
+                vals = [v if ok else None for v, ok in zip(vals, valid)]
+            lists.append(vals)
+            continue
         vals = c.to_pylist()
         if c.dtype.is_float:
             vals = ["NaN" if (v is not None and isinstance(v, float) and math.isnan(v)) else v for v in vals]
@@ -200,6 +294,7 @@ def group_ids(cols: List[Column]) -> Tuple[torch.Tensor, torch.Tensor]:
     if not _use_native(device):
         return group_ids_ref(cols)
     lib = native.lib()
+    cols = _key_cols(cols)
     hashes = murmur3(cols)
     cap = _next_pow2(2 * n)
     slots = torch.full((cap,), -1, dtype=torch.int32, device=device)
@@ -276,7 +371,7 @@ def join_build(build_cols: List[Column]) -> Optional["JoinTable"]:
     lib = native.lib()
     sp = native.stream_ptr(device)
     n_build = len(build_cols[0])
-    bhash = murmur3(build_cols)
+    bhash = _join_hash(build_cols)
     cap = _next_pow2(2 * max(n_build, 1))
     heads = torch.full((cap,), -1, dtype=torch.int32, device=device)
     nxt = torch.empty(max(n_build, 1), dtype=torch.int32, device=device)
@@ -306,8 +401,8 @@ def _join_key_descs(build_cols, probe_cols):
     kernels that take key descriptors by value."""
     import numpy as np
 
-    barr, bkeep = native.pack_descs_host(build_cols)
-    parr, pkeep = native.pack_descs_host(probe_cols)
+    barr, bkeep = native.pack_descs_host(_key_cols(build_cols))
+    parr, pkeep = native.pack_descs_host(_key_cols(probe_cols))
     return np.concatenate([barr, parr]), (bkeep, pkeep)
 
 
@@ -390,7 +485,8 @@ def _hash_join_legacy(build_cols, probe_cols, emit_unmatched_probe,
     lib = native.lib()
     sp = native.stream_ptr(device)
     heads, nxt, cap, bhash = table.heads, table.nxt, table.cap, table.bhash
-    phash = murmur3(probe_cols)
+    build_cols, probe_cols = _key_cols(build_cols), _key_cols(probe_cols)
+    phash = _join_hash(probe_cols)
     bdescs, bkeep = native.pack_descs(build_cols, device)
     pdescs, pkeep = native.pack_descs(probe_cols, device)
     counts = torch.zeros(n_probe, dtype=torch.int32, device=device)
@@ -462,8 +558,9 @@ def join_counts(build_cols: List[Column], probe_cols: List[Column]) -> torch.Ten
         return counts
     lib = native.lib()
     sp = native.stream_ptr(device)
-    bhash = murmur3(build_cols)
-    phash = murmur3(probe_cols)
+    build_cols, probe_cols = _key_cols(build_cols), _key_cols(probe_cols)
+    bhash = _join_hash(build_cols)
+    phash = _join_hash(probe_cols)
     cap = _next_pow2(2 * max(n_build, 1))
     heads = torch.full((cap,), -1, dtype=torch.int32, device=device)
     nxt = torch.empty(max(n_build, 1), dtype=torch.int32, device=device)
