@@ -443,6 +443,10 @@ def _aggregate(w: _Window, wf: WindowFunc, name: str) -> Column:
             # partition) share the value at the LAST peer row
             out = out.gather(L.peers().end)
         return out
+    # whole-partition aggregate (no ORDER BY, no frame): the GROUP BY
+    # kernels, so float MIN/MAX follow the aggregate rule (NaN the greatest
+    # value: MIN skips NaN unless all are NaN), whereas the frame and running
+    # paths above keep "NaN propagates" into both MIN and MAX
     acc, cnt = ops.agg_scatter(L.seg, max(L.nseg, 1), val, fn)
     return ex._finalize_agg(AggFunc(fn, None, name=name), val.dtype, acc,
                             cnt).gather(L.seg)

@@ -203,6 +203,13 @@ def pack_descs_host(cols) -> Tuple[np.ndarray, list]:
             # the kernels load a limb pair in one 16-byte access
             raise ValueError("decimal128 key column is not 16-byte aligned "
                              "(ops._key_cols aligns it)")
+        for part in (col.offsets, col.validity):
+            # a host buffer beside device data would hand the kernels a host
+            # pointer. Column.to() cannot mend such a column: it returns
+            # early when the data tensor already sits on the target device
+            if part is not None and part.device != data.device:
+                raise ValueError(f"column buffers on {data.device} and "
+                                 f"{part.device}: move the whole Column")
         keep.append(data)
         arr[i]["data"] = data.data_ptr()
         if col.offsets is not None:

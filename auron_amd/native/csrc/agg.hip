@@ -8,7 +8,8 @@
 // atomic scatter on fp64 (rocprof: 5.5s per 14M-row scatter).
 //
 // value dtypes: f64 (code 0), i64 (code 1), i32 (code 2), f32 (code 3).
-// ops: sum=0, min=1, max=2. Accumulators are f64 or i64 (widened).
+// ops: sum=0, min=1, max=2. Sums accumulate in f64 or i64 (widened); MIN
+// and MAX always in i64, floats as their order keys (f64_order_key).
 // count (valid-row count per group) accumulates alongside when
 // `counts` is non-null.
 
@@ -24,26 +25,19 @@ static inline int agg_grid(int64_t n) {
   return (int)g;
 }
 
-__device__ __forceinline__ void atomic_min_f64(double* addr, double v) {
-  unsigned long long* a = (unsigned long long*)addr;
-  unsigned long long old = *a, assumed;
-  do {
-    assumed = old;
-    double cur = __longlong_as_double((long long)assumed);
-    if (v >= cur) return;
-    old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
-  } while (old != assumed);
-}
-
-__device__ __forceinline__ void atomic_max_f64(double* addr, double v) {
-  unsigned long long* a = (unsigned long long*)addr;
-  unsigned long long old = *a, assumed;
-  do {
-    assumed = old;
-    double cur = __longlong_as_double((long long)assumed);
-    if (v <= cur) return;
-    old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
-  } while (old != assumed);
+// Float MIN/MAX run on int64 order keys, not on the doubles: the key of a
+// double is its bit pattern with the low 63 bits flipped when the sign is
+// set, every NaN first replaced by the canonical 0x7ff8000000000000. Signed
+// integer order on the keys is then the aggregate order
+//   -inf < ... < -0.0 < 0.0 < ... < +inf < NaN
+// (NaN the greatest value: MAX is NaN if any input is, MIN only if all
+// are), the result no longer depends on lane position or on which atomic
+// lands first, and the int64 identities INT64_MAX / INT64_MIN lie outside
+// the keys of all doubles, so a group of NaNs alone still leaves the
+// identity. The host decodes the accumulator (ops._f64_from_order_keys).
+__device__ __forceinline__ int64_t f64_order_key(double v) {
+  int64_t b = (v != v) ? (int64_t)0x7ff8000000000000ll : __double_as_longlong(v);
+  return b ^ ((b >> 63) & INT64_MAX);
 }
 
 __device__ __forceinline__ void atomic_min_i64(int64_t* addr, int64_t v) {
@@ -82,9 +76,8 @@ __global__ void k_agg_scatter(const int64_t* gids, int64_t n, const uint8_t* val
     int64_t i = base + lane;
     bool live = i < n && (!validity || validity[i]);
     int64_t g = (i < n) ? gids[i] : (int64_t)-1;
-    if (ACC_F64) {
-      double ident = op == 0 ? 0.0 : (op == 1 ? INFINITY : -INFINITY);
-      double v = live ? (double)values[i] : ident;
+    if (ACC_F64 && op == 0) {
+      double v = live ? (double)values[i] : 0.0;
       int64_t c = live ? 1 : 0;
       // head-flag segmented inclusive scan (a gid may recur in separate
       // runs within the wave; plain gid-equality folding would double
@@ -97,9 +90,7 @@ __global__ void k_agg_scatter(const int64_t* gids, int64_t n, const uint8_t* val
         int pf = __shfl_up(flag, d, 64);
         if (lane >= d) {
           if (!flag) {
-            if (op == 0) v += pv;
-            else if (op == 1) v = v < pv ? v : pv;
-            else v = v > pv ? v : pv;
+            v += pv;
             c += pc;
           }
           flag = flag || pf;
@@ -108,15 +99,14 @@ __global__ void k_agg_scatter(const int64_t* gids, int64_t n, const uint8_t* val
       int64_t ng = __shfl_down(g, 1, 64);
       bool seg_last = (lane == 63) || (ng != g);
       if (seg_last && g >= 0 && c > 0) {
-        double* a = (double*)acc;
         if (counts) atomicAdd((unsigned long long*)&counts[g], (unsigned long long)c);
-        if (op == 0) atomicAdd(&a[g], v);
-        else if (op == 1) atomic_min_f64(&a[g], v);
-        else atomic_max_f64(&a[g], v);
+        atomicAdd(&((double*)acc)[g], v);
       }
     } else {
+      // integer values, and float MIN/MAX on order keys
       int64_t ident = op == 0 ? 0 : (op == 1 ? INT64_MAX : INT64_MIN);
-      int64_t v = live ? (int64_t)values[i] : ident;
+      int64_t v = !live ? ident
+                  : ACC_F64 ? f64_order_key((double)values[i]) : (int64_t)values[i];
       int64_t c = live ? 1 : 0;
       int64_t pg1 = __shfl_up(g, 1, 64);
       int flag = (lane == 0) || (pg1 != g);
@@ -154,24 +144,6 @@ __global__ void k_agg_scatter(const int64_t* gids, int64_t n, const uint8_t* val
 // atomics are per-CU, no cross-XCD traffic), then flush once per group
 // per block. Selected by the host when ngroups fits in 64 KB of LDS and
 // n is large enough to amortize the flush.
-__device__ __forceinline__ void lds_min_f64(unsigned long long* a, double v) {
-  unsigned long long old = *a, assumed;
-  do {
-    assumed = old;
-    if (v >= __longlong_as_double((long long)assumed)) return;
-    old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
-  } while (old != assumed);
-}
-
-__device__ __forceinline__ void lds_max_f64(unsigned long long* a, double v) {
-  unsigned long long old = *a, assumed;
-  do {
-    assumed = old;
-    if (v <= __longlong_as_double((long long)assumed)) return;
-    old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
-  } while (old != assumed);
-}
-
 __device__ __forceinline__ void lds_min_i64(unsigned long long* a, int64_t v) {
   unsigned long long old = *a, assumed;
   do {
@@ -208,13 +180,10 @@ __global__ void k_agg_scatter_lds(const int64_t* gids, int64_t n,
     if (validity && !validity[i]) continue;
     int g = (int)gids[i];
     if (scnt) atomicAdd(&scnt[g], 1ull);
-    if (ACC_F64) {
-      double v = (double)values[i];
-      if (op == 0) atomicAdd((double*)&sacc[g], v);
-      else if (op == 1) lds_min_f64(&sacc[g], v);
-      else lds_max_f64(&sacc[g], v);
+    if (ACC_F64 && op == 0) {
+      atomicAdd((double*)&sacc[g], (double)values[i]);
     } else {
-      int64_t v = (int64_t)values[i];
+      int64_t v = ACC_F64 ? f64_order_key((double)values[i]) : (int64_t)values[i];
       if (op == 0) atomicAdd(&sacc[g], (unsigned long long)v);
       else if (op == 1) lds_min_i64(&sacc[g], v);
       else lds_max_i64(&sacc[g], v);
@@ -224,12 +193,8 @@ __global__ void k_agg_scatter_lds(const int64_t* gids, int64_t n,
   for (int i = threadIdx.x; i < ngroups; i += blockDim.x) {
     if (scnt && scnt[i]) atomicAdd((unsigned long long*)&counts[i], scnt[i]);
     if (sacc[i] == init_bits) continue;  // untouched (or identity: no-op)
-    if (ACC_F64) {
-      double v = __longlong_as_double((long long)sacc[i]);
-      double* a = (double*)acc;
-      if (op == 0) atomicAdd(&a[i], v);
-      else if (op == 1) atomic_min_f64(&a[i], v);
-      else atomic_max_f64(&a[i], v);
+    if (ACC_F64 && op == 0) {
+      atomicAdd(&((double*)acc)[i], __longlong_as_double((long long)sacc[i]));
     } else {
       int64_t v = (int64_t)sacc[i];
       int64_t* a = (int64_t*)acc;
@@ -247,6 +212,7 @@ __global__ void k_agg_scatter_lds(const int64_t* gids, int64_t n,
 // AggDesc layout (int64 x 6, packed host-side):
 //   [0]=values ptr [1]=validity ptr(0=none) [2]=vtype(0 f64,1 i64,2 i32,3 f32)
 //   [3]=op(0 sum,1 min,2 max) [4]=acc ptr [5]=counts ptr(0=none)
+// acc is f64 for a float sum and i64 for everything else (see f64_order_key)
 struct AggDesc {
   const void* values;
   const uint8_t* validity;
@@ -287,33 +253,30 @@ __global__ void k_agg_multi(const int64_t* gids, int64_t n, const AggDesc* descs
       bool f64p = d.vtype == 0 || d.vtype == 3;
       int64_t c = live ? 1 : 0;
       int flag = head;
-      if (f64p) {
-        double ident = d.op == 0 ? 0.0 : (d.op == 1 ? INFINITY : -INFINITY);
-        double v = live ? agg_load_f64(d.values, d.vtype, i) : ident;
+      if (f64p && d.op == 0) {
+        double v = live ? agg_load_f64(d.values, d.vtype, i) : 0.0;
         for (int dd = 1; dd < 64; dd <<= 1) {
           double pv = __shfl_up(v, dd, 64);
           int64_t pc = __shfl_up(c, dd, 64);
           int pf = __shfl_up(flag, dd, 64);
           if (lane >= dd) {
             if (!flag) {
-              if (d.op == 0) v += pv;
-              else if (d.op == 1) v = v < pv ? v : pv;
-              else v = v > pv ? v : pv;
+              v += pv;
               c += pc;
             }
             flag = flag || pf;
           }
         }
         if (seg_last && g >= 0 && c > 0) {
-          double* acc = (double*)d.acc;
           if (d.counts) atomicAdd((unsigned long long*)&d.counts[g], (unsigned long long)c);
-          if (d.op == 0) atomicAdd(&acc[g], v);
-          else if (d.op == 1) atomic_min_f64(&acc[g], v);
-          else atomic_max_f64(&acc[g], v);
+          atomicAdd(&((double*)d.acc)[g], v);
         }
       } else {
+        // integer values, and float MIN/MAX on order keys
         int64_t ident = d.op == 0 ? 0 : (d.op == 1 ? INT64_MAX : INT64_MIN);
-        int64_t v = live ? agg_load_i64(d.values, d.vtype, i) : ident;
+        int64_t v = !live ? ident
+                    : f64p ? f64_order_key(agg_load_f64(d.values, d.vtype, i))
+                           : agg_load_i64(d.values, d.vtype, i);
         for (int dd = 1; dd < 64; dd <<= 1) {
           int64_t pv = __shfl_up(v, dd, 64);
           int64_t pc = __shfl_up(c, dd, 64);
@@ -392,14 +355,7 @@ AU_EXPORT int au_agg_scatter(const int64_t* gids, int64_t n, const uint8_t* vali
   if (use_lds) {
     unsigned long long init;
     if (op == 0) init = 0ull;  // sum identity (0.0 and 0 share the bit pattern)
-    else if (acc_f64) {
-      double d = op == 1 ? INFINITY : -INFINITY;
-      unsigned long long bits;
-      __builtin_memcpy(&bits, &d, 8);  // host-side double_as_longlong
-      init = bits;
-    } else {
-      init = (unsigned long long)(op == 1 ? INT64_MAX : INT64_MIN);
-    }
+    else init = (unsigned long long)(op == 1 ? INT64_MAX : INT64_MIN);  // keys too
     int64_t g64 = (n + 255) / 256;
     int64_t cap = n / (16 * ngroups) + 1;  // keep flush << accumulate
     if (g64 > cap) g64 = cap;

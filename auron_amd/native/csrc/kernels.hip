@@ -157,15 +157,19 @@ __device__ uint32_t hash_one(const AuColDesc& c, int64_t i, uint32_t seed) {
     case AU_DECIMAL64:
     case AU_TIMESTAMP:
       return hash_long((uint64_t)((const int64_t*)c.data)[i], seed);
+    // floats as Spark's floatToIntBits / doubleToLongBits see them: -0.0 as
+    // 0.0 and every NaN (either sign, any payload) as the one canonical NaN,
+    // so keys that compare equal in keys_equal hash alike
     case AU_FLOAT32: {
       float f = ((const float*)c.data)[i];
       if (f == 0.0f) f = 0.0f;  // normalize -0.0
-      return hash_int(__float_as_uint(f), seed);
+      return hash_int(f != f ? 0x7fc00000u : __float_as_uint(f), seed);
     }
     case AU_FLOAT64: {
       double d = ((const double*)c.data)[i];
       if (d == 0.0) d = 0.0;
-      return hash_long((uint64_t)__double_as_longlong(d), seed);
+      return hash_long(d != d ? 0x7ff8000000000000ull
+                              : (uint64_t)__double_as_longlong(d), seed);
     }
     case AU_STRING: {
       int64_t s = c.offsets[i];
@@ -230,12 +234,18 @@ __device__ bool keys_equal(const AuColDesc* a_cols, int64_t ai,
       case AU_TIMESTAMP:
         if (((const int64_t*)a.data)[ai] != ((const int64_t*)b.data)[bi]) return false;
         break;
-      case AU_FLOAT32:
-        if (((const float*)a.data)[ai] != ((const float*)b.data)[bi]) return false;
+      // float keys: -0.0 == 0.0 and NaN == NaN (Spark's grouping and join
+      // rule; IEEE != alone makes every NaN row a group of its own)
+      case AU_FLOAT32: {
+        const float x = ((const float*)a.data)[ai], y = ((const float*)b.data)[bi];
+        if (x != y && !(x != x && y != y)) return false;
         break;
-      case AU_FLOAT64:
-        if (((const double*)a.data)[ai] != ((const double*)b.data)[bi]) return false;
+      }
+      case AU_FLOAT64: {
+        const double x = ((const double*)a.data)[ai], y = ((const double*)b.data)[bi];
+        if (x != y && !(x != x && y != y)) return false;
         break;
+      }
       case AU_STRING: {
         int64_t as = a.offsets[ai], ae = a.offsets[ai + 1];
         int64_t bs = b.offsets[bi], be = b.offsets[bi + 1];

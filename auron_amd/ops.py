@@ -123,7 +123,8 @@ def murmur3_ref(cols: List[Column], seed: int = SPARK_SEED) -> torch.Tensor:
     """Pure-torch Spark Murmur3_x86_32, bit-exact vs the HIP kernel.
 
     Reference semantics: spark_hash.rs (seed-chained per column, nulls
-    skipped, -0.0 normalized, strings hashed as UTF-8 bytes, decimals by
+    skipped, -0.0 normalized, every NaN hashed as the canonical one,
+    timestamps as longs, strings hashed as UTF-8 bytes, decimals by
     precision: <= 18 as the unscaled long, wider as the minimal big-endian
     bytes of the unscaled value).
     """
@@ -147,16 +148,20 @@ def murmur3_ref(cols: List[Column], seed: int = SPARK_SEED) -> torch.Tensor:
             elif code in (dtypes.INT8, dtypes.INT16, dtypes.INT32, dtypes.DATE32):
                 v = d.to(torch.int64) & _M32
                 hv = _hash_int_t(v, h)
-            elif code in (dtypes.INT64, dtypes.DECIMAL64):
+            elif code in (dtypes.INT64, dtypes.DECIMAL64, dtypes.TIMESTAMP):
                 v = d.to(torch.int64)
                 hv = _hash_long_t(v, h)
             elif code == dtypes.FLOAT32:
+                # floatToIntBits: -0.0 as 0.0, every NaN as 0x7fc00000
                 f = torch.where(d == 0, torch.zeros_like(d), d)
                 v = f.view(torch.int32).to(torch.int64) & _M32
+                v = torch.where(torch.isnan(d), torch.full_like(v, 0x7FC00000), v)
                 hv = _hash_int_t(v, h)
             elif code == dtypes.FLOAT64:
+                # doubleToLongBits: -0.0 as 0.0, every NaN as 0x7ff8000000000000
                 f = torch.where(d == 0, torch.zeros_like(d), d)
                 v = f.view(torch.int64)
+                v = torch.where(torch.isnan(d), torch.full_like(v, 0x7FF8 << 48), v)
                 hv = _hash_long_t(v, h)
             elif code == dtypes.DECIMAL128:
                 if _spark_narrow_decimal(c.dtype):
@@ -254,6 +259,26 @@ def _key_tuple_lists(cols: List[Column]):
                     zip(d[:, 0].tolist(), d[:, 1].tolist())]
             if valid is not None:
                 vals = [v if ok else None for v, ok in zip(vals, valid)]
+            lists.append(vals)
+            continue
+        if c.dtype.code == dtypes.DECIMAL64:
+            # exact unscaled ints as well: dividing by the scale merges
+            # neighbouring values beyond 2**53
+            vals = c.data.tolist()
+            if c.validity is not None:
+                vals = [v if ok else None
+                        for v, ok in zip(vals, c.validity.tolist())]
+            lists.append(vals)
+            continue
+        if c.dtype.is_string:
+            # the bytes themselves: decoding merges strings that differ only
+            # inside invalid UTF-8
+            raw = c.data.to("cpu").numpy().tobytes()
+            offs = c.offsets.tolist()
+            vals = [raw[offs[i]:offs[i + 1]] for i in range(len(c))]
+            if c.validity is not None:
+                vals = [v if ok else None
+                        for v, ok in zip(vals, c.validity.tolist())]
             lists.append(vals)
             continue
         vals = c.to_pylist()
@@ -1492,6 +1517,44 @@ def partition_order(part_ids: torch.Tensor, nparts: int) -> Tuple[torch.Tensor, 
 
 
 # ============================================================== aggregation
+_I64_MAX = torch.iinfo(torch.int64).max
+_I64_MIN = torch.iinfo(torch.int64).min
+
+
+def _f64_order_keys(v: torch.Tensor) -> torch.Tensor:
+    """float64 -> int64 keys whose integer order is the aggregate MIN/MAX
+    order of the floats: -inf < ... < -0.0 < 0.0 < ... < +inf < NaN, every
+    NaN being the one canonical NaN (f64_order_key in csrc/agg.hip). Both
+    int64 identities lie outside the keys of all floats, so a group of
+    NaNs alone still leaves the identity."""
+    bits = torch.where(torch.isnan(v), torch.full_like(v, float("nan")), v)
+    bits = bits.contiguous().view(torch.int64)
+    return torch.where(bits < 0, bits ^ _I64_MAX, bits)
+
+
+def _f64_from_order_keys(k: torch.Tensor) -> torch.Tensor:
+    """Inverse of _f64_order_keys. An identity (a group with no valid row)
+    decodes to some NaN: such accumulators are unspecified."""
+    return torch.where(k < 0, k ^ _I64_MAX, k).view(torch.float64)
+
+
+def _agg_init(op: int, acc_f64: bool):
+    """(accumulator dtype, identity): sums accumulate in f64 / i64; MIN and
+    MAX in int64 for every input, floats as their order keys."""
+    if op == 0:
+        return (torch.float64, 0.0) if acc_f64 else (torch.int64, 0)
+    return torch.int64, (_I64_MAX if op == 1 else _I64_MIN)
+
+
+def _agg_minmax_out(acc: torch.Tensor, values: Column) -> torch.Tensor:
+    """MIN/MAX accumulator -> the input dtype (state keeps the input dtype,
+    reference acc.rs semantics), on every path."""
+    tgt = values.data.dtype
+    if tgt.is_floating_point:
+        acc = _f64_from_order_keys(acc)
+    return acc if acc.dtype == tgt else acc.to(tgt)
+
+
 def _agg_scatter_native(gids: torch.Tensor, num_groups: int, values: Column, fn: str):
     """HIP atomic scatter-accumulate (csrc/agg.hip). torch's fp64
     scatter_add_ measured ~400x slower on gfx950 (rocprof, q23)."""
@@ -1515,26 +1578,16 @@ def _agg_scatter_native(gids: torch.Tensor, num_groups: int, values: Column, fn:
     vtype = {torch.float64: 0, torch.int64: 1, torch.int32: 2, torch.float32: 3}[v.dtype]
     acc_f64 = v.dtype in (torch.float32, torch.float64)
     op = {"sum": 0, "avg": 0, "min": 1, "max": 2}[fn]
-    if op == 0:
-        init = 0.0 if acc_f64 else 0
-    elif op == 1:
-        init = float("inf") if acc_f64 else torch.iinfo(torch.int64).max
-    else:
-        init = float("-inf") if acc_f64 else torch.iinfo(torch.int64).min
-    acc = torch.full((num_groups,), init,
-                     dtype=torch.float64 if acc_f64 else torch.int64, device=device)
+    acc_dtype, init = _agg_init(op, acc_f64)
+    acc = torch.full((num_groups,), init, dtype=acc_dtype, device=device)
     rc = lib.au_agg_scatter(g.data_ptr(), n, vptr, v.data_ptr(), vtype, op,
                             1 if acc_f64 else 0, acc.data_ptr(), counts.data_ptr(),
                             num_groups, sp)
     native.check(rc, "au_agg_scatter")
     del keep
     if fn in ("min", "max"):
-        # state keeps the input dtype (reference acc.rs semantics)
-        tgt = values.data.dtype if values.data.dtype not in (torch.int8, torch.int16, torch.bool) else torch.int64
-        if acc.dtype != tgt:
-            acc = acc.to(tgt)
-    elif fn in ("sum", "avg") and values.data.dtype == torch.float32:
-        pass  # f64 accumulator is the widened sum dtype
+        acc = _agg_minmax_out(acc, values)
+    # sums: the f64 / i64 accumulator is the widened sum dtype
     return acc, counts
 
 
@@ -1566,15 +1619,8 @@ def agg_scatter_multi(gids: torch.Tensor, num_groups: int, items):
                  torch.float32: 3}[v.dtype]
         acc_f64 = v.dtype in (torch.float32, torch.float64)
         op = {"sum": 0, "avg": 0, "min": 1, "max": 2}[fn]
-        if op == 0:
-            init = 0.0 if acc_f64 else 0
-        elif op == 1:
-            init = float("inf") if acc_f64 else torch.iinfo(torch.int64).max
-        else:
-            init = float("-inf") if acc_f64 else torch.iinfo(torch.int64).min
-        acc = torch.full((num_groups,), init,
-                         dtype=torch.float64 if acc_f64 else torch.int64,
-                         device=device)
+        acc_dtype, init = _agg_init(op, acc_f64)
+        acc = torch.full((num_groups,), init, dtype=acc_dtype, device=device)
         counts = torch.zeros(num_groups, dtype=torch.int64, device=device)
         vptr = 0
         if values.validity is not None:
@@ -1594,10 +1640,7 @@ def agg_scatter_multi(gids: torch.Tensor, num_groups: int, items):
     res = []
     for values, fn, acc, counts in outs:
         if fn in ("min", "max"):
-            tgt = values.data.dtype if values.data.dtype not in \
-                (torch.int8, torch.int16, torch.bool) else torch.int64
-            if acc.dtype != tgt:
-                acc = acc.to(tgt)
+            acc = _agg_minmax_out(acc, values)
         res.append((acc, counts))
     return res
 
@@ -1626,6 +1669,14 @@ def agg_scatter(gids: torch.Tensor, num_groups: int, values: Column, fn: str):
 
     -> (acc tensor [G], count-of-valid [G] int64). Nulls are excluded.
     GPU: hand-written atomic scatter kernels; CPU: torch scatter_reduce.
+
+    The same on both paths: SUM is int64 (wrapping) over integers and
+    bools, plain IEEE float64 over floats (NaN and +-inf propagate).
+    MIN/MAX return the input dtype, bool included; over floats NaN is the
+    greatest value (Spark): MAX is NaN if any valid input is, MIN only if
+    all are, and -0.0 equals 0.0. Window frame min/max differ: there NaN
+    propagates into both (window_frame_minmax). The accumulator of a group
+    with count 0 is unspecified.
     """
     device = gids.device
     if num_groups > 0 and _use_native(device):
@@ -1644,17 +1695,20 @@ def agg_scatter(gids: torch.Tensor, num_groups: int, values: Column, fn: str):
     if fn in ("sum", "avg"):
         if v.dtype in (torch.float32,):
             v = v.to(torch.float64)
-        if v.dtype in (torch.int8, torch.int16, torch.int32):
+        if v.dtype in (torch.int8, torch.int16, torch.int32, torch.bool):
             v = v.to(torch.int64)
         acc = torch.zeros(num_groups, dtype=v.dtype, device=device)
         acc.scatter_add_(0, g, v)
         return acc, cnt
     if fn in ("min", "max"):
+        # the native path's rule: int64 accumulators, floats as order keys
+        # (NaN above +inf, MIN is NaN only for a group of NaNs), identities
+        # outside every value, result in the input dtype
         red = "amin" if fn == "min" else "amax"
-        init = torch.finfo(v.dtype).max if v.dtype.is_floating_point else torch.iinfo(v.dtype).max
-        if fn == "max":
-            init = torch.finfo(v.dtype).min if v.dtype.is_floating_point else torch.iinfo(v.dtype).min
-        acc = torch.full((num_groups,), init, dtype=v.dtype, device=device)
-        acc.scatter_reduce_(0, g, v, reduce=red, include_self=True)
-        return acc, cnt
+        k = _f64_order_keys(v.to(torch.float64)) if v.dtype.is_floating_point \
+            else v.to(torch.int64)
+        acc = torch.full((num_groups,), _I64_MAX if fn == "min" else _I64_MIN,
+                         dtype=torch.int64, device=device)
+        acc.scatter_reduce_(0, g, k, reduce=red, include_self=True)
+        return _agg_minmax_out(acc, values), cnt
     raise ValueError(fn)

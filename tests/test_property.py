@@ -7,6 +7,7 @@ property tests play that role — they sweep input shapes (nulls, empties,
 duplicates, extremes, unicode) that the curated TPC-DS data misses.
 """
 import math
+import re
 
 import pytest
 from hypothesis import given, settings, strategies as st
@@ -103,7 +104,10 @@ def test_like_contains_matches_python(vals, pat):
     b = _batch({"s": vals}, {"s": dtypes.string})
     plan = P.Filter(P.MemoryScan([b]), col("s").like(f"%{pat}%"))
     got = AuronSession().collect(plan).to_pydict()["s"]
-    ref = [v for v in vals if v is not None and pat in v]
+    # `pat in v`, except that a generated '_' or '%' is a LIKE wildcard
+    rx = re.compile(".*" + "".join(".*" if ch == "%" else "." if ch == "_"
+                                   else re.escape(ch) for ch in pat) + ".*", re.S)
+    ref = [v for v in vals if v is not None and rx.fullmatch(v)]
     assert got == ref
 
 
