@@ -13,6 +13,20 @@ Spark null semantics implemented here:
  - arithmetic/comparison propagate null (validity AND)
  - AND/OR use Kleene 3-valued logic
  - x / 0 and x % 0 yield null (non-ANSI Spark behavior)
+
+Value rules (tests/expr_oracle.py states them in full and both this
+evaluator and the fused kernel are tested against it):
+ - `%` takes the sign of the dividend, for floats too (fmod); x % -1 is 0.
+   Float `%` on host tensors goes through numpy's fmod: torch's vectorised
+   CPU fmod returns NaN where a / b overflows (1.5 % 5e-324)
+ - decimal64 -> float64 is one correctly rounded division by a tensor
+   divisor (unscale_decimal64): by a Python scalar the device multiplies
+   with the reciprocal, 1 ulp off
+ - float -> integer casts: NaN is 0, then truncate and saturate at the
+   int64 bounds (int64) or the int32 bounds (narrower types, which wrap)
+ - float/int -> decimal64 rounds half to even; NaN, +-inf and overflow
+   become null
+ - float comparisons: NaN == NaN, NaN is greater than every other value
 """
 from __future__ import annotations
 
@@ -272,17 +286,72 @@ def _cast_col(c: Column, dt: DataType) -> Column:
         data = c.data * (10 ** diff) if diff >= 0 else torch.div(c.data, 10 ** (-diff), rounding_mode="trunc")
         return Column(dt, data, c.validity)
     if c.dtype.code == dtypes.DECIMAL64:
-        f = c.data.to(torch.float64) / (10 ** c.dtype.scale)
+        f = unscale_decimal64(c.data, c.dtype.scale)
         if dt.is_float:
             return Column(dt, f.to(dt.torch_dtype), c.validity)
+        if dt.code in _FLOAT_TO_INT_BITS:
+            return Column(dt, _float_to_int(f, dt), c.validity)
         return Column(dt, f.to(dt.torch_dtype), c.validity)
     if dt.code == dtypes.DECIMAL64:
-        scaled = torch.round(c.data.to(torch.float64) * (10 ** dt.scale)).to(torch.int64)
-        return Column(dt, scaled, c.validity)
-    if c.dtype.is_float and dt.is_integer:
-        # Spark cast double->int truncates toward zero
-        return Column(dt, c.data.trunc().to(dt.torch_dtype), c.validity)
+        scaled = torch.round(c.data.to(torch.float64) * (10 ** dt.scale))
+        if (not c.dtype.is_float and c.dtype.code != dtypes.INT64
+                and dt.scale <= 9):
+            # at most 2^31 * 10^9 < 2^63: a narrow integer cannot overflow,
+            # so it pays for no mask and keeps its validity as it is
+            return Column(dt, scaled.to(torch.int64), c.validity)
+        # round half to even; NaN, +-inf and a product outside int64 become
+        # null (precision is not enforced). Mask, never probe: no sync
+        ok = (scaled >= -_TWO63) & (scaled < _TWO63)  # false for NaN
+        data = torch.where(ok, scaled, torch.zeros_like(scaled)).to(torch.int64)
+        valid = ok if c.validity is None else (c.validity & ok)
+        return Column(dt, data, compact_validity(valid))
+    if c.dtype.is_float and dt.code in _FLOAT_TO_INT_BITS:
+        return Column(dt, _float_to_int(c.data, dt), c.validity)
     return Column(dt, c.data.to(dt.torch_dtype), c.validity)
+
+
+_POW10 = {}  # (device, scale) -> 0-dim float64 tensor holding 10**scale
+
+
+def unscale_decimal64(data: torch.Tensor, scale: int) -> torch.Tensor:
+    """decimal64 -> float64: float(unscaled) / float(10**scale), ONE
+    correctly rounded division, which is what Spark's toDouble gives and
+    what k_expr_exec's DIVD computes. The divisor is a tensor on purpose:
+    on the device torch turns division by a Python scalar into a
+    multiplication by its reciprocal, 1 ulp off for about one value in
+    ten. The 0-dim divisor is made once per device and scale by a fill,
+    so nothing is copied from the host and nothing syncs."""
+    key = (data.device, scale)
+    div = _POW10.get(key)
+    if div is None:
+        div = _POW10[key] = torch.full((), float(10 ** scale),
+                                       dtype=torch.float64,
+                                       device=data.device)
+    return data.to(torch.float64) / div
+
+
+_TWO63 = 9223372036854775808.0  # (double)INT64_MAX rounds up to this
+_FLOAT_TO_INT_BITS = {dtypes.INT8: 8, dtypes.INT16: 16, dtypes.INT32: 32,
+                      dtypes.DATE32: 32, dtypes.INT64: 64}
+
+
+def _float_to_int(f: torch.Tensor, dt: DataType) -> torch.Tensor:
+    """Spark's non-ANSI double -> integral cast: NaN is 0, everything else
+    truncates toward zero and saturates at the int64 bounds (int64) or at
+    the int32 bounds (int32, int16, int8 -- the narrower two then wrap, as
+    the JVM's d.toInt.toShort does). Every value is brought in range while
+    still a double: an out-of-range float -> int conversion is whatever
+    the host or the device happens to do."""
+    f = f.to(torch.float64)
+    t = torch.where(f != f, torch.zeros_like(f), f.trunc())
+    if _FLOAT_TO_INT_BITS[dt.code] == 64:
+        # INT64_MAX is no double: 2^63 and above are set after the cast
+        big = t >= _TWO63
+        t = torch.where(big, torch.zeros_like(t), t).clamp(min=-_TWO63)
+        i = t.to(torch.int64)
+        return torch.where(big, torch.full_like(i, (1 << 63) - 1), i)
+    i = t.clamp(min=-2147483648.0, max=2147483647.0).to(torch.int32)
+    return i.to(dt.torch_dtype)  # int -> narrower int wraps
 
 
 def dec128_to_float64(data: torch.Tensor, scale: int) -> torch.Tensor:
@@ -375,7 +444,7 @@ def _cast_decimal128(c: Column, dt: DataType) -> Column:
                                          dt.precision, c.validity)
         return Column(dt, data, compact_validity(valid))
     as64 = _cast_col(c, dtypes.decimal64(18, dt.scale))
-    return Column(dt, dec64_to_dec128(as64.data), c.validity)
+    return Column(dt, dec64_to_dec128(as64.data), as64.validity)
 
 
 def _parse_decimal128(v: str, dt: DataType):
@@ -536,6 +605,19 @@ class TryCast(Expr):
         return _cast_col(self.child.eval(batch), self.to)
 
 
+def _float_fmod(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """C fmod, which is exact. torch.fmod is that on the device; its
+    vectorised CPU kernel returns NaN wherever a / b overflows (1.5 % 5e-324
+    is 0), so host tensors go through numpy's fmod instead."""
+    if a.device.type != "cpu":
+        return torch.fmod(a, b)
+    import numpy as np
+
+    with np.errstate(invalid="ignore"):
+        out = np.fmod(a.contiguous().numpy(), b.contiguous().numpy())
+    return torch.from_numpy(out)
+
+
 @dataclass(eq=False)
 class Arith(Expr):
     op: str
@@ -576,11 +658,15 @@ class Arith(Expr):
                     data = a.to(torch.float64) / b.to(torch.float64)
                 else:
                     data = a / b
+            elif dt.is_float:
+                # Spark % is Java's: the sign of the dividend (fmod);
+                # torch.remainder takes the divisor's
+                data = _float_fmod(a, b)
             else:
-                data = torch.remainder(a, b)
-                if dt.is_integer:
-                    # Spark % takes sign of dividend (fmod), torch.remainder takes divisor sign
-                    data = a - torch.div(a, b, rounding_mode="trunc") * b
+                # x % -1 is 0, like x % 1: dividing the type minimum by -1
+                # traps on x86 (SIGFPE), so -1 never reaches the division
+                b = torch.where(b == -1, torch.ones_like(b), b)
+                data = a - torch.div(a, b, rounding_mode="trunc") * b
         else:
             raise ValueError(self.op)
         if self.op == "/" and dt.is_integer:
@@ -612,10 +698,48 @@ class Cmp(Expr):
             return Column(dtypes.bool_, data, combine_validity(l, r))
         if dtypes.is_decimal128_op(l.dtype, r.dtype):
             return _dec128_cmp(self.op, l, r)
-        l, r, _ = _promote(l, r)
+        # only a float operand can hold NaN: a decimal or integer promoted
+        # to float64 cannot, nor can a literal that is not NaN itself
+        l_nan = l.dtype.is_float
+        r_nan = r.dtype.is_float and not (
+            isinstance(self.right, Literal)
+            and isinstance(self.right.value, float)
+            and self.right.value == self.right.value)
+        l, r, dt = _promote(l, r)
         a, b = l.data, r.data
-        fn = {"==": torch.eq, "!=": torch.ne, "<": torch.lt, "<=": torch.le, ">": torch.gt, ">=": torch.ge}[self.op]
-        return Column(dtypes.bool_, fn(a, b), combine_validity(l, r))
+        if dt.is_float and (l_nan or r_nan):
+            data = _nan_ordered(self.op, a, b, l_nan, r_nan)
+        else:
+            fn = {"==": torch.eq, "!=": torch.ne, "<": torch.lt, "<=": torch.le, ">": torch.gt, ">=": torch.ge}[self.op]
+            data = fn(a, b)
+        return Column(dtypes.bool_, data, combine_validity(l, r))
+
+
+def _nan_ordered(op: str, a, b, a_nan: bool, b_nan: bool) -> torch.Tensor:
+    """Spark's float comparison: NaN equals NaN and is greater than every
+    other value, +inf included (the rule GROUP BY, joins and DISTINCT apply
+    to keys). a_nan / b_nan say which side can hold a NaN at all, so a
+    comparison pays only for the launches it can need: none beyond IEEE's
+    for column-vs-literal, one for `col < col` against a NaN-free left
+    side, three at the most. Masks only: nothing reads a value back."""
+    if op in (">", ">="):  # a > b is b < a
+        a, b, a_nan, b_nan = b, a, b_nan, a_nan
+        op = "<" if op == ">" else "<="
+    if op in ("==", "!="):
+        if not (a_nan and b_nan):
+            return torch.eq(a, b) if op == "==" else torch.ne(a, b)
+        eq = torch.eq(a, b) | ((a != a) & (b != b))
+        return eq if op == "==" else ~eq
+    if not b_nan:  # IEEE is already false for a NaN on the left
+        return torch.lt(a, b) if op == "<" else torch.le(a, b)
+    if op == "<":
+        # a < b or only b is NaN: not(a >= b) is that plus "a is NaN"
+        lt = ~torch.ge(a, b)
+        return (lt & (a == a)) if a_nan else lt
+    # a <= b, or b is NaN
+    if not a_nan:
+        return ~torch.gt(a, b)
+    return torch.le(a, b) | (b != b)
 
 
 @dataclass(eq=False)
@@ -755,7 +879,7 @@ class InList(Expr):
             m = strings.isin(c, [v for v in self.values if v is not None])
             return Column(dtypes.bool_, m, c.validity)
         vals = torch.tensor([v for v in self.values if v is not None], dtype=c.dtype.torch_dtype if c.dtype.code != dtypes.DECIMAL64 else torch.float64, device=c.device)
-        data = c.data if c.dtype.code != dtypes.DECIMAL64 else c.data.to(torch.float64) / 10 ** c.dtype.scale
+        data = c.data if c.dtype.code != dtypes.DECIMAL64 else unscale_decimal64(c.data, c.dtype.scale)
         m = torch.isin(data, vals)
         return Column(dtypes.bool_, m, c.validity)
 

@@ -16,7 +16,7 @@ import torch
 from . import dtypes, strings
 from .column import Column, compact_validity
 from .exprs import (Expr, _all_valid, _cast_col, _civil_from_days,
-                    combine_validity)
+                    combine_validity, unscale_decimal64)
 
 # executor-injected evaluation context (partition id etc.)
 EVAL_CONTEXT: contextvars.ContextVar = contextvars.ContextVar(
@@ -1323,7 +1323,7 @@ class ArrayContains(Expr):
         row = torch.repeat_interleave(
             torch.arange(n, dtype=torch.int64, device=device), lens)
         if c.dtype.child.code == dtypes.DECIMAL64:
-            hit = c.data.to(torch.float64) / 10 ** c.dtype.scale == float(self.value)
+            hit = unscale_decimal64(c.data, c.dtype.scale) == float(self.value)
         else:
             hit = c.data == self.value
         # uint8 accumulator: the device scatter_reduce_ has no bool kernel

@@ -9,10 +9,24 @@ by ONE HIP kernel (native/csrc/fused.hip), reading every input column
 once and writing only the final outputs.
 
 Semantics mirror exprs.py exactly (promotion rules, Kleene logic, null
-cond -> false, /0 -> null, Spark integer `/` as double division).
-Unsupported nodes (strings, float32, windows, subqueries) make
-compile_exprs return None for that expr and the caller falls back to
-the interpreted eval.
+cond -> false, /0 -> null, Spark integer `/` as double division), and
+both are held to tests/expr_oracle.py, which states the rules:
+ - narrow integers wrap after every operator: ADDI/SUBI/MULI work on
+   64-bit slots, so a TRUNC_I follows each one whose type is narrower
+ - x % -1 is 0, also at the type minimum
+ - float -> int: NaN is 0, then truncate and saturate at the int64 bounds
+   (int64) or the int32 bounds (int32/16/8, which then wrap)
+ - float/int -> decimal64 rounds half to even; NaN, +-inf and overflow
+   become null
+ - float comparisons: NaN == NaN and NaN is the greatest value
+ - decimal64 -> float64 is one correctly rounded division (DIVD here, a
+   tensor divisor in exprs.unscale_decimal64), never a reciprocal multiply
+ - float `%` is not compiled; eval computes C's fmod (on host tensors
+   through numpy, because torch's vectorised CPU fmod returns NaN where
+   a / b overflows)
+Unsupported nodes (strings, float32, timestamp casts, float `%`, windows,
+subqueries) make compile_exprs skip that expr and the caller falls back
+to the interpreted eval.
 """
 from __future__ import annotations
 
@@ -175,6 +189,9 @@ class _Compiler:
             return
         if frm.is_string or to.is_string:
             raise _Unsupported("string cast")
+        if dtypes.TIMESTAMP in (frm.code, to.code):
+            # seconds/days <-> micros scaling lives in exprs._cast_timestamp
+            raise _Unsupported("timestamp cast")
         if frm.code == dtypes.DECIMAL64 and to.code == dtypes.DECIMAL64:
             diff = to.scale - frm.scale
             if diff >= 0:
@@ -191,12 +208,7 @@ class _Compiler:
             if not _is_d(to):
                 if to.code == dtypes.BOOL:
                     raise _Unsupported("decimal->bool")
-                self.op(D2I_TRUNC)
-                bits = _INT_BITS.get(to.code)
-                if bits is None:
-                    raise _Unsupported("decimal cast target")
-                if bits < 64:
-                    self.op(TRUNC_I, 0, bits)
+                self.d2i(to)
             elif to.code == dtypes.FLOAT32:
                 raise _Unsupported("float32")
             return
@@ -215,18 +227,38 @@ class _Compiler:
         if _is_d(frm) and not _is_d(to):
             if to.code == dtypes.BOOL:
                 raise _Unsupported("float->bool")
-            self.op(D2I_TRUNC)
-            bits = _INT_BITS[to.code]
-            if bits < 64:
-                self.op(TRUNC_I, 0, bits)
+            self.d2i(to)
             return
         # int-family to int-family
         if to.code == dtypes.BOOL:
             self.op(NEZ)
             return
-        fb, tb = _INT_BITS[frm.code], _INT_BITS[to.code]
+        fb, tb = self.int_bits(frm), self.int_bits(to)
         if tb < fb:
             self.op(TRUNC_I, 0, tb)
+
+    def int_bits(self, dt: DataType) -> int:
+        bits = _INT_BITS.get(dt.code)
+        if bits is None:
+            raise _Unsupported(f"not an integer-family type: {dt}")
+        return bits
+
+    def wrap(self, dt: DataType):
+        """The slot is 64 bits wide: wrap the top slot to dt's width so a
+        narrow result overflows exactly as the typed eval path does."""
+        if dt.code == dtypes.TIMESTAMP:
+            return  # micros in a full 64-bit slot: ts - ts needs no TRUNC_I
+        bits = self.int_bits(dt)
+        if 1 < bits < 64:
+            self.op(TRUNC_I, 0, bits)
+
+    def d2i(self, to: DataType):
+        """double -> integer family: saturate at 64 bits for int64, at 32
+        for everything narrower (the JVM's d.toInt.toShort), then wrap."""
+        bits = self.int_bits(to)
+        self.op(D2I_TRUNC, 0, 64 if bits == 64 else 32)
+        if bits < 32:
+            self.op(TRUNC_I, 0, bits)
 
     def to_bool(self, dt: DataType):
         if dt.code != dtypes.BOOL:
@@ -329,6 +361,7 @@ class _Compiler:
                 self.op({"+": ADDD, "-": SUBD, "*": MULD}[e.op], d=-1)
             else:
                 self.op({"+": ADDI, "-": SUBI, "*": MULI}[e.op], d=-1)
+                self.wrap(dt)
             return dt
         if e.op == "/":
             if not _is_d(tgt):

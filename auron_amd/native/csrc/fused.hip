@@ -18,6 +18,18 @@
 // SQL three-valued logic: every slot carries a null bit; arithmetic and
 // comparisons propagate nulls, AND/OR are Kleene, IFELSE treats a null
 // condition as false, DIV/MOD by zero yields null (non-ANSI Spark).
+//
+// Value rules (Spark non-ANSI; tests/expr_oracle.py states them in full):
+//  - integer slots are 64 bits wide; the host emits TRUNC_I after every
+//    ADDI/SUBI/MULI whose result type is narrower, so narrow integers wrap
+//    between operators and not only at OUT
+//  - MODI: sign of the dividend, x % -1 == 0 (also at the type minimum)
+//  - D2I_TRUNC: NaN -> 0, else truncate toward zero and saturate at the
+//    int32 or int64 bounds (imm = 32 | 64); TRUNC_I then wraps to int8/16
+//  - D2I_ROUND (-> decimal64): round half to even; NaN, +-inf and values
+//    outside [-2^63, 2^63) make the slot null
+//  - double comparisons: NaN == NaN, NaN is greater than everything else
+//    (+inf included), -0.0 == 0.0 -- the rule GROUP BY and joins use
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -123,11 +135,29 @@ __global__ void __launch_bounds__(EX_BLOCK) k_expr_exec(
           ExVal v; v.d = (double)STK(sp - 1); STK(sp - 1) = v.i; break;
         }
         case EX_D2I_TRUNC: {
-          ExVal v; v.i = STK(sp - 1); STK(sp - 1) = (int64_t)v.d; break;
+          // bounds are compared in double BEFORE converting: an out-of-
+          // range (int64_t)d is undefined, and (double)INT64_MAX is 2^63
+          ExVal v; v.i = STK(sp - 1);
+          const double d = v.d;
+          int64_t r;
+          if (d != d) r = 0;
+          else if (ins.imm == 32)
+            r = d >= 2147483647.0 ? 2147483647LL
+                : d <= -2147483648.0 ? -2147483648LL : (int64_t)d;
+          else
+            r = d >= 9223372036854775808.0 ? INT64_MAX
+                : d <= -9223372036854775808.0 ? INT64_MIN : (int64_t)d;
+          STK(sp - 1) = r; break;
         }
         case EX_D2I_ROUND: {
           ExVal v; v.i = STK(sp - 1);
-          STK(sp - 1) = (int64_t)nearbyint(v.d); break;
+          const double r = nearbyint(v.d);
+          // NaN fails both tests; +-inf and overflow fail one
+          const bool ok = r >= -9223372036854775808.0 &&
+                          r < 9223372036854775808.0;
+          STK(sp - 1) = ok ? (int64_t)r : 0;
+          if (!ok) nulls |= 1u << (sp - 1);
+          break;
         }
         case EX_TRUNC_I: {
           int sh = 64 - (int)ins.imm;
@@ -151,7 +181,10 @@ __global__ void __launch_bounds__(EX_BLOCK) k_expr_exec(
             case EX_EQI: r = a == b; break;
             case EX_NEI: r = a != b; break;
             case EX_DIVI: if (b == 0) nl = true; else r = a / b; break;
-            case EX_MODI: if (b == 0) nl = true; else r = a % b; break;
+            case EX_MODI:
+              // a % -1 is 0; evaluating it at INT64_MIN is undefined
+              if (b == 0) nl = true; else if (b != -1) r = a % b;
+              break;
           }
           sp--; STK(sp - 1) = r;
           if (nl) nulls |= 1u << (sp - 1); else nulls &= ~(1u << (sp - 1));
@@ -164,17 +197,18 @@ __global__ void __launch_bounds__(EX_BLOCK) k_expr_exec(
           double a = va.d, b = vb.d;
           ExVal r; r.i = 0;
           bool nl = (nulls >> (sp - 1) & 1u) | (nulls >> (sp - 2) & 1u);
+          const bool an = a != a, bn = b != b;  // NaN is the greatest value
           switch (ins.op) {
             case EX_ADDD: r.d = a + b; break;
             case EX_SUBD: r.d = a - b; break;
             case EX_MULD: r.d = a * b; break;
             case EX_DIVD: if (b == 0.0) nl = true; else r.d = a / b; break;
-            case EX_LTD: r.i = a < b; break;
-            case EX_LED: r.i = a <= b; break;
-            case EX_GTD: r.i = a > b; break;
-            case EX_GED: r.i = a >= b; break;
-            case EX_EQD: r.i = a == b; break;
-            case EX_NED: r.i = a != b; break;
+            case EX_LTD: r.i = (a < b) || (bn && !an); break;
+            case EX_LED: r.i = (a <= b) || bn; break;
+            case EX_GTD: r.i = (a > b) || (an && !bn); break;
+            case EX_GED: r.i = (a >= b) || an; break;
+            case EX_EQD: r.i = (a == b) || (an && bn); break;
+            case EX_NED: r.i = !((a == b) || (an && bn)); break;
           }
           sp--; STK(sp - 1) = r.i;
           if (nl) nulls |= 1u << (sp - 1); else nulls &= ~(1u << (sp - 1));
