@@ -22,12 +22,12 @@ import torch
 import torch.distributed as dist
 
 from .. import dtypes, ops
-from ..column import Column, RecordBatch, adjacent_equal, compact_validity
-from ..dtypes import DataType
+from ..column import Column, RecordBatch, adjacent_equal
 from ..exchange import all_gather_batch, all_to_all
-from ..exprs import AggFunc, Col
+from ..exprs import Col
 from ..plan import nodes as P
-from ..config import AGG_STREAMING, BROADCAST_CACHE_BYTES, AuronConf
+from ..config import BROADCAST_CACHE_BYTES, AuronConf
+from .agg import exec_hash_agg, group_rows
 from .window import exec_window
 
 
@@ -73,13 +73,6 @@ class ExecContext:
                 ctx.metrics[key] = ctx.metrics.get(key, 0.0) + time.perf_counter() - self.t0
 
         return _T()
-
-
-# agg fns whose state is mergeable across chunks (everything _merge_states
-# can combine); count_distinct / collect_* need the whole group resident
-_SPLITTABLE_AGGS = frozenset(
-    {"sum", "avg", "min", "max", "count", "count_star",
-     "first", "first_ignores_null"})
 
 
 # integer key widths as decimal(p, 0) against a decimal128 key
@@ -1389,46 +1382,7 @@ class Executor:
 
     # -------------------------------------------------------------- hash agg
     def _exec_HashAgg(self, node: P.HashAgg) -> List[RecordBatch]:
-        from ..exprs import eval_scope
-
-        stream_ok = (AuronConf().get(AGG_STREAMING)
-                     and self._est_input_bytes(node.child)
-                     > self._stream_bytes_threshold())
-        if node.mode == "partial" and stream_ok:
-            # streaming partial agg (agg_table.rs analogue): inputs are
-            # consumed chunk-by-chunk, states re-merged when they shrink,
-            # and the accumulated state registers with the memmgr so it
-            # can spill under pressure — the whole input never has to be
-            # resident at once
-            return self._exec_hash_agg_partial_chunked(node)
-        if (node.mode == "complete" and stream_ok
-                and all(a.fn in _SPLITTABLE_AGGS for a in node.aggs)
-                and (node.keys or self.ctx.world_size == 1)):
-            # (keyless complete at W>1 keeps the one-shot path: its
-            # emit-null-row-only-on-rank-0 rule lives in _hash_agg_body)
-            # W=1 collapses partial+exchange+final towers to one complete
-            # agg (see _rewrite) — stream it when the input is large:
-            # chunk the child into partial states, then run ONE final pass
-            # over the merged states (the distributed composition), so a
-            # rollup over a SF>=100 fact join never materializes. Small
-            # inputs (peeked below one chunk) keep the one-pass grouping.
-            import itertools
-
-            it = self.execute_iter(node.child)
-            buf, rest = self._peek_stream(it)
-            if rest is None:
-                bb = _concat(buf)
-                with eval_scope(bb):
-                    return self._hash_agg_body(node, bb)
-            part = P.HashAgg(node.child, node.keys, node.aggs, mode="partial")
-            states = _concat(self._exec_hash_agg_partial_chunked(
-                part, batches=itertools.chain(buf, rest)))
-            fin = P.HashAgg(node.child, node.keys, node.aggs, mode="final")
-            with eval_scope(states):
-                return self._hash_agg_body(fin, states)
-        b = _concat(self.execute(node.child))
-        with eval_scope(b):
-            return self._hash_agg_body(node, b)
+        return exec_hash_agg(self, node)
 
     def _est_input_bytes(self, node: P.PlanNode) -> int:
         """Static, rank-deterministic size estimate of a subtree's output
@@ -1464,530 +1418,6 @@ class Executor:
             _, total = torch.cuda.mem_get_info()
             return int(total * 0.08)
         return 1 << 30
-
-    def _peek_stream(self, it, threshold: Optional[int] = None):
-        """Pull from a batch iterator until `threshold` rows are buffered.
-        Returns (buffered, rest_iterator) — rest is None when the stream
-        was exhausted under the threshold (small input: the caller should
-        take the cheaper one-shot path; the chunk/merge machinery only
-        pays for itself when the input is genuinely large)."""
-        if threshold is None:
-            from ..config import STREAM_PEEK_FACTOR
-
-            threshold = AuronConf().get(STREAM_PEEK_FACTOR) * self.ctx.batch_rows
-        buf: List[RecordBatch] = []
-        rows = 0
-        for b in it:
-            buf.append(b)
-            rows += b.num_rows
-            if rows > threshold:
-                return buf, it
-        return buf, None
-
-    def _exec_hash_agg_partial_chunked(self, node: P.HashAgg,
-                                       batches=None) -> List[RecordBatch]:
-        import itertools
-
-        from ..exprs import eval_scope
-
-        if batches is None:
-            buf, rest = self._peek_stream(self.execute_iter(node.child))
-            if rest is None:
-                bb = _concat(buf)
-                with eval_scope(bb):
-                    return self._hash_agg_body(node, bb)
-            batches = itertools.chain(buf, rest)
-        schema_batch: Optional[RecordBatch] = None
-        limit = self.ctx.batch_rows
-        acc: List[RecordBatch] = []
-        acc_rows = 0
-        merge_worthwhile = True
-        holder = self.ctx.memmgr.register("agg-partial-state", acc)
-
-        def flush_merge():
-            nonlocal acc, acc_rows, merge_worthwhile, holder
-            cur = holder.batches()
-            merged = self._merge_states(node, _concat(cur)) if cur else None
-            holder.release()
-            if merged is not None:
-                if merged.num_rows > 0.8 * acc_rows:
-                    # low-reduction keys: stop paying for re-merges; the
-                    # post-exchange final agg regroups anyway
-                    merge_worthwhile = False
-                acc = [merged]
-                acc_rows = merged.num_rows
-            else:
-                acc = []
-                acc_rows = 0
-            holder = self.ctx.memmgr.register("agg-partial-state", acc)
-
-        for b in batches:
-            if schema_batch is None:
-                schema_batch = b.slice(0, 0)
-            for lo in range(0, max(b.num_rows, 1), limit):
-                chunk = b if b.num_rows <= limit else \
-                    b.slice(lo, min(limit, b.num_rows - lo))
-                with eval_scope(chunk):
-                    out = self._hash_agg_body(node, chunk)
-                cur = holder.batches()
-                cur.extend(out)
-                acc_rows += sum(x.num_rows for x in out)
-                holder.refresh()
-                if b.num_rows <= limit:
-                    break
-            if merge_worthwhile and acc_rows > 2 * limit:
-                flush_merge()
-        result = holder.batches()
-        holder.release()
-        if not result:
-            # preserve the empty-input partial schema (the child stream is
-            # consumed; a 0-row slice of its first batch carries the schema)
-            assert schema_batch is not None, "child stream yielded no batches"
-            with eval_scope(schema_batch):
-                return self._hash_agg_body(node, schema_batch)
-        return result
-
-    def _merge_states(self, node: P.HashAgg, b: RecordBatch) -> RecordBatch:
-        """Combine partial-state rows with equal keys into one state row
-        (state schema in, state schema out — the pre-exchange self-merge
-        of the reference's in-memory agg table)."""
-        device = b.device
-        key_cols = [Col(a.name).eval(b) for a in node.keys]
-        if key_cols:
-            gids, reps = ops.group_ids(key_cols)
-            ngroups = int(reps.numel())
-            out_keys = [c.gather(reps) for c in key_cols]
-        else:
-            gids = torch.zeros(b.num_rows, dtype=torch.int64, device=device)
-            ngroups = 1 if b.num_rows else 0
-            out_keys = []
-        names = [a.name for a in node.keys]
-        cols = list(out_keys)
-        for i, agg in enumerate(node.aggs):
-            s0 = b.column(f"__agg{i}_0")
-            s1 = b.column(f"__agg{i}_1")
-            merged_cnt, _ = ops.agg_scatter(gids, ngroups, s1, "sum")
-            if agg.fn in ("count", "count_star"):
-                cols.append(Column(dtypes.int64, merged_cnt))
-                names.append(f"__agg{i}_0")
-                cols.append(Column(dtypes.int64, merged_cnt))
-                names.append(f"__agg{i}_1")
-                continue
-            comb = {"sum": "sum", "avg": "sum", "min": "min", "max": "max",
-                    "first": "first", "first_ignores_null": "first"}[agg.fn]
-            if comb == "first":
-                acc_col, _ = self._agg_first(gids, ngroups, s0)
-                cols.append(acc_col)
-            elif comb == "sum" and s0.dtype.code == dtypes.DECIMAL128:
-                data, cnt = self._sum128_scatter(gids, ngroups, s0)
-                cols.append(Column(s0.dtype, data, compact_validity(cnt > 0)))
-            elif comb == "sum" and self._decimal_sum_unsafe(s0, b.num_rows):
-                data, cnt = self._sum_split_exact(gids, ngroups, s0)
-                cols.append(Column(s0.dtype, data, cnt > 0))
-            else:
-                data, cnt = ops.agg_scatter(gids, ngroups, s0, comb)
-                if isinstance(data, Column):
-                    cols.append(data)
-                else:
-                    cols.append(Column(s0.dtype, data, compact_validity(cnt > 0)))
-            names.append(f"__agg{i}_0")
-            cols.append(Column(dtypes.int64, merged_cnt))
-            names.append(f"__agg{i}_1")
-        return RecordBatch(names, cols)
-
-    def _hash_agg_body(self, node: P.HashAgg, b: RecordBatch) -> List[RecordBatch]:
-        device = b.device
-        n = b.num_rows
-        if node.mode == "final":
-            key_cols = [Col(a.name).eval(b) for a in node.keys]
-        else:
-            key_cols = [a.expr.eval(b) for a in node.keys]
-        if node.keys:
-            if node.mode == "partial" and self._partial_skip(key_cols, n):
-                return [self._partial_passthrough(node, b, key_cols)]
-            gids, reps = ops.group_ids(key_cols)
-            ngroups = int(reps.numel())
-            out_keys = [c.gather(reps) for c in key_cols]
-        else:
-            gids = torch.zeros(n, dtype=torch.int64, device=device)
-            # a keyless (global) agg over an empty input yields one null row
-            # in SQL — but distributed, only the rank holding the gathered
-            # rows (rank 0 after an Exchange "single") may emit it, else
-            # every rank would contribute a duplicate
-            if n == 0 and node.mode in ("final", "complete") and self.ctx.rank != 0:
-                ngroups = 0
-            else:
-                ngroups = 1
-            out_keys = []
-        names = [a.name for a in node.keys]
-        cols = list(out_keys)
-        # fuse plain sum/avg/min/max aggregates into ONE kernel pass
-        # (k_agg_multi): gids are read once, head flags computed once
-        fused: Dict[int, tuple] = {}
-        if node.mode in ("partial", "complete") and ngroups > 0:
-            fuse_items = []
-            fuse_idx = []
-            for i, agg in enumerate(node.aggs):
-                if agg.fn in ("sum", "avg", "min", "max") and agg.expr is not None:
-                    v = agg.expr.eval(b)
-                    if v.dtype.code == dtypes.DECIMAL128:
-                        continue  # two-limb path below
-                    if agg.fn == "sum" and self._sum_needs_128(v.dtype):
-                        continue  # decimal128 result path below
-                    if agg.fn in ("sum", "avg") and self._decimal_sum_unsafe(v, n):
-                        continue  # exact split path below
-                    fuse_items.append((v, agg.fn))
-                    fuse_idx.append(i)
-            if len(fuse_items) > 1:
-                for i, res in zip(fuse_idx,
-                                  ops.agg_scatter_multi(gids, ngroups, fuse_items)):
-                    fused[i] = (fuse_items[fuse_idx.index(i)][0], res)
-        for i, agg in enumerate(node.aggs):
-            s0, s1 = f"__agg{i}_0", f"__agg{i}_1"
-            if node.mode == "final":
-                sv = b.column(s0)
-                sc = b.column(s1)
-                merged_cnt, _ = ops.agg_scatter(gids, ngroups, sc, "sum")
-                if agg.fn in ("count", "count_star"):
-                    cols.append(Column(dtypes.int64, merged_cnt))
-                    names.append(agg.name)
-                    continue
-                comb = {"sum": "sum", "avg": "sum", "min": "min", "max": "max",
-                        "first": "first", "first_ignores_null": "first"}[agg.fn]
-                if comb == "first":
-                    acc, cnt = self._agg_first(gids, ngroups, sv)
-                elif comb == "sum" and sv.dtype.code == dtypes.DECIMAL128:
-                    data, cnt = self._sum128_scatter(gids, ngroups, sv)
-                    acc = Column(sv.dtype, data, compact_validity(cnt > 0))
-                elif comb == "sum" and self._decimal_sum_unsafe(sv, n):
-                    acc, cnt = self._sum_split_exact(gids, ngroups, sv)
-                else:
-                    acc, cnt = ops.agg_scatter(gids, ngroups, sv, comb)
-                cols.append(self._finalize_agg(agg, sv.dtype, acc, merged_cnt,
-                                                widen=False))
-                names.append(agg.name)
-            else:
-                val = agg.expr.eval(b) if agg.expr is not None else None
-                if agg.fn == "count_star":
-                    cnt = ops.agg_count_star(gids, ngroups)
-                    acc, vcnt, vdt = cnt, cnt, dtypes.int64
-                elif agg.fn == "count_distinct":
-                    assert node.mode == "complete", "count_distinct needs complete mode (pre-exchanged)"
-                    d_gids, d_reps = ops.group_ids(key_cols + [val])
-                    og = gids[d_reps]
-                    vv = val.validity[d_reps] if val.validity is not None else None
-                    if vv is not None:
-                        og = og[vv]
-                    cnt = torch.zeros(ngroups, dtype=torch.int64, device=device)
-                    if og.numel():
-                        cnt.scatter_add_(0, og, torch.ones(og.numel(), dtype=torch.int64, device=device))
-                    acc, vcnt, vdt = cnt, cnt, dtypes.int64
-                elif agg.fn in ("collect_list", "collect_set"):
-                    assert node.mode == "complete", \
-                        "collect_* needs complete mode (pre-exchanged)"
-                    acc_col = self._agg_collect(gids, ngroups, val,
-                                                dedupe=agg.fn == "collect_set",
-                                                key_cols=key_cols)
-                    cnt = ops.agg_scatter(gids, ngroups, val, "count")[1]
-                    acc, vcnt, vdt = acc_col, cnt, acc_col.dtype
-                elif agg.fn in ("first", "first_ignores_null"):
-                    acc_col, cnt = self._agg_first(gids, ngroups, val)
-                    acc, vcnt, vdt = acc_col, cnt, val.dtype
-                elif i in fused:
-                    fval, (facc, fcnt) = fused[i]
-                    acc, vcnt, vdt = facc, fcnt, fval.dtype
-                elif agg.fn == "sum" and self._sum_needs_128(val.dtype):
-                    # declared result exceeds the 64-bit backing: exact
-                    # 128-bit limbs (state schema is static -> SPMD-safe)
-                    if val.dtype.code == dtypes.DECIMAL128:
-                        data, vcnt = self._sum128_scatter(gids, ngroups, val)
-                    else:
-                        data, vcnt = self._sum_split_128(gids, ngroups, val)
-                    vdt = val.dtype
-                    acc = Column(self._state_dtype(agg, vdt), data,
-                                 compact_validity(vcnt > 0))
-                elif agg.fn in ("sum", "avg") and self._decimal_sum_unsafe(val, n):
-                    acc, vcnt = self._sum_split_exact(gids, ngroups, val)
-                    vdt = val.dtype
-                else:
-                    fn = {"sum": "sum", "avg": "sum", "min": "min", "max": "max", "count": "count"}[agg.fn]
-                    acc, vcnt, vdt = *ops.agg_scatter(gids, ngroups, val, fn), val.dtype
-                if node.mode == "partial":
-                    state_dt = self._state_dtype(agg, vdt)
-                    if isinstance(acc, Column):
-                        cols.append(acc)
-                    else:
-                        cols.append(Column(state_dt, acc, (vcnt > 0) if agg.fn not in ("count", "count_star", "count_distinct") else None))
-                    names.append(s0)
-                    cols.append(Column(dtypes.int64, vcnt))
-                    names.append(s1)
-                else:  # complete
-                    if agg.fn in ("count", "count_star", "count_distinct"):
-                        cols.append(Column(dtypes.int64, acc))
-                    else:
-                        a_data = acc.data if isinstance(acc, Column) else acc
-                        cols.append(self._finalize_agg(agg, vdt, a_data if not isinstance(acc, Column) else acc, vcnt))
-                    names.append(agg.name)
-        return [RecordBatch(names, cols)]
-
-    @staticmethod
-    def _decimal_sum_unsafe(val: Column, nrows: int) -> bool:
-        """True when a plain int64 scatter-sum of this decimal column could
-        wrap (advisor finding r1: n*maxabs must fit int64)."""
-        if val.dtype.code != dtypes.DECIMAL64 or nrows == 0:
-            return False
-        m = int(val.data.abs().max().item())
-        return m > 0 and nrows * m >= (1 << 62)
-
-    def _sum_split_raw(self, gids, ngroups, val: Column):
-        """Split int64 addends into 32-bit digit accumulators (exact for
-        <2^31 rows): returns (h, rem, cnt) with group total = h*2^32+rem."""
-        device = gids.device
-        n = gids.numel()
-        assert n < (1 << 31), "batch too large for split accumulation"
-        valid = val.validity if val.validity is not None else \
-            torch.ones(n, dtype=torch.bool, device=device)
-        x = torch.where(valid, val.data, torch.zeros_like(val.data))
-        lo = x & 0xFFFFFFFF
-        hi = x >> 32
-        sum_lo = torch.zeros(ngroups, dtype=torch.int64, device=device)
-        sum_hi = torch.zeros(ngroups, dtype=torch.int64, device=device)
-        cnt = torch.zeros(ngroups, dtype=torch.int64, device=device)
-        if n:
-            sum_lo.scatter_add_(0, gids, lo)
-            sum_hi.scatter_add_(0, gids, hi)
-            cnt.scatter_add_(0, gids, valid.to(torch.int64))
-        carry = sum_lo >> 32
-        rem = sum_lo & 0xFFFFFFFF
-        h = sum_hi + carry
-        return h, rem, cnt
-
-    def _sum_split_exact(self, gids, ngroups, val: Column):
-        """Exact decimal sum via hi/lo 32-bit split accumulators: each
-        int64 addend is split into (v>>32, v&0xffffffff); both partial
-        sums stay far from int64 range for <2^31 rows, and the recombine
-        detects true overflow of the mathematical result instead of
-        silently wrapping (sum(decimal) with p+10>18 routes to the
-        decimal128 path instead of this one)."""
-        h, rem, cnt = self._sum_split_raw(gids, ngroups, val)
-        if bool(((h < -(1 << 31)) | (h > (1 << 31) - 1)).any()):
-            from ..session import AuronTaskError
-
-            raise AuronTaskError(
-                "decimal sum overflow: group total exceeds 18 significant "
-                "digits (decimal64 backing); rescale or cast to double")
-        return h * (1 << 32) + rem, cnt
-
-    def _sum_split_128(self, gids, ngroups, val: Column):
-        """Exact sum of decimal64 addends into decimal128 limbs.
-
-        total = h*2^32 + rem with rem in [0,2^32); two's-complement
-        128-bit limbs are lo = (h<<32)+rem (bit pattern) and
-        hi = h>>32 (arithmetic = floor(h/2^32))."""
-        h, rem, cnt = self._sum_split_raw(gids, ngroups, val)
-        lo = (h << 32) + rem
-        hi = h >> 32
-        return torch.stack([lo, hi], dim=1), cnt
-
-    @staticmethod
-    def _sum_needs_128(vdt: DataType) -> bool:
-        return (vdt.code == dtypes.DECIMAL64 and vdt.precision + 10 > 18) \
-            or vdt.code == dtypes.DECIMAL128
-
-    def _sum128_scatter(self, gids, ngroups, col: Column):
-        """Exact group sum of a decimal128 [n,2] column: the 128-bit value
-        is split into four 32-bit digits (top digit signed), each digit
-        scatter-summed in int64, then recomposed with carry propagation —
-        no digit sum can overflow below 2^31 rows."""
-        device = gids.device
-        n = gids.numel()
-        assert n < (1 << 31), "batch too large for split accumulation"
-        valid = col.validity if col.validity is not None else \
-            torch.ones(n, dtype=torch.bool, device=device)
-        z = torch.zeros((), dtype=torch.int64, device=device)
-        lo = torch.where(valid, col.data[:, 0], z)
-        hi = torch.where(valid, col.data[:, 1], z)
-        m = 0xFFFFFFFF
-        digs = [lo & m, (lo >> 32) & m, hi & m, hi >> 32]
-        sums = []
-        cnt = torch.zeros(ngroups, dtype=torch.int64, device=device)
-        for d in digs:
-            sd = torch.zeros(ngroups, dtype=torch.int64, device=device)
-            if n:
-                sd.scatter_add_(0, gids, d)
-            sums.append(sd)
-        if n:
-            cnt.scatter_add_(0, gids, valid.to(torch.int64))
-        c = sums[0] >> 32
-        r0 = sums[0] & m
-        t1 = sums[1] + c
-        r1 = t1 & m
-        t2 = sums[2] + (t1 >> 32)
-        r2 = t2 & m
-        t3 = sums[3] + (t2 >> 32)
-        out_lo = (r1 << 32) | r0
-        out_hi = (t3 << 32) | r2
-        return torch.stack([out_lo, out_hi], dim=1), cnt
-
-    def _partial_skip(self, key_cols, n: int) -> bool:
-        """Partial-agg skipping (conf.rs:39-42): sample the reduction
-        ratio; when grouping barely reduces rows, skip the hash table and
-        emit singleton states — the post-exchange final agg regroups."""
-        if n < (1 << 14):
-            return False
-        from ..config import PARTIAL_AGG_SKIPPING_RATIO, AuronConf
-
-        ratio = AuronConf().get(PARTIAL_AGG_SKIPPING_RATIO)
-        if ratio >= 1.0:
-            return False
-        sn = min(n, 1 << 16)
-        idx = torch.arange(sn, dtype=torch.int64, device=key_cols[0].device)
-        sample = [c.gather(idx) for c in key_cols]
-        _, reps = ops.group_ids(sample)
-        return int(reps.numel()) > ratio * sn
-
-    def _partial_passthrough(self, node: P.HashAgg, b: RecordBatch,
-                             key_cols) -> RecordBatch:
-        """Each row becomes its own group: states carry the raw value and
-        a 0/1 count. Schema-identical to the grouped partial output."""
-        n = b.num_rows
-        device = b.device
-        names = [a.name for a in node.keys]
-        cols = list(key_cols)
-        for i, agg in enumerate(node.aggs):
-            s0, s1 = f"__agg{i}_0", f"__agg{i}_1"
-            val = agg.expr.eval(b) if agg.expr is not None else None
-            if agg.fn == "count_star":
-                ones = torch.ones(n, dtype=torch.int64, device=device)
-                cols.append(Column(dtypes.int64, ones))
-                names.append(s0)
-                cols.append(Column(dtypes.int64, ones))
-                names.append(s1)
-                continue
-            valid = val.validity if val.validity is not None else \
-                torch.ones(n, dtype=torch.bool, device=device)
-            cnt = valid.to(torch.int64)
-            if agg.fn == "count":
-                cols.append(Column(dtypes.int64, cnt))
-                names.append(s0)
-                cols.append(Column(dtypes.int64, cnt))
-                names.append(s1)
-                continue
-            state_dt = self._state_dtype(agg, val.dtype)
-            data = val.data
-            if (state_dt.code == dtypes.DECIMAL128
-                    and val.dtype.code == dtypes.DECIMAL64):
-                from ..exprs import dec64_to_dec128
-
-                data = dec64_to_dec128(data)
-            elif data.dtype != state_dt.torch_dtype and not state_dt.uses_offsets:
-                data = data.to(state_dt.torch_dtype)
-            cols.append(Column(state_dt, data, val.validity, val.offsets))
-            names.append(s0)
-            cols.append(Column(dtypes.int64, cnt))
-            names.append(s1)
-        return RecordBatch(names, cols)
-
-    def _agg_first(self, gids, ngroups, val: Column):
-        """first value per group, skipping nulls (the reference's
-        first_ignores_null; plain `first` maps here too — order is
-        engine-dependent in Spark anyway)."""
-        device = gids.device
-        n = gids.numel()
-        order = torch.arange(n, dtype=torch.int64, device=device)
-        valid = val.validity
-        g = gids
-        o = order
-        if valid is not None:
-            g = gids[valid]
-            o = order[valid]
-        first_row = torch.full((ngroups,), n, dtype=torch.int64, device=device)
-        if g.numel():
-            first_row.scatter_reduce_(0, g, o, reduce="amin", include_self=True)
-        cnt = torch.zeros(ngroups, dtype=torch.int64, device=device)
-        if g.numel():
-            cnt.scatter_add_(0, g, torch.ones_like(g))
-        safe = first_row.clamp(max=max(n - 1, 0))
-        col = val.gather(safe)
-        v = (cnt > 0)
-        if col.validity is not None:
-            v = v & col.validity
-        return Column(val.dtype, col.data, v, col.offsets), cnt
-
-    def _state_dtype(self, agg: AggFunc, vdt: DataType) -> DataType:
-        if agg.fn in ("count", "count_star", "count_distinct"):
-            return dtypes.int64
-        if agg.fn in ("sum", "avg"):
-            if vdt.code == dtypes.DECIMAL128:
-                return dtypes.decimal128(38, vdt.scale)
-            if vdt.code == dtypes.DECIMAL64:
-                if agg.fn == "sum" and vdt.precision + 10 > 18:
-                    # exceeds the 64-bit backing: two-limb accumulator
-                    return dtypes.decimal128(vdt.precision + 10, vdt.scale)
-                return dtypes.decimal64(min(vdt.precision + 10, 38), vdt.scale)
-            if vdt.is_integer or vdt.code == dtypes.BOOL:
-                return dtypes.int64
-            return dtypes.float64
-        return vdt  # min/max/first keep input type
-
-    def _agg_collect(self, gids, ngroups, val: Column, dedupe: bool,
-                     key_cols) -> Column:
-        """collect_list / collect_set -> LIST column, one row per group
-        (agg/collect.rs analogue). Null inputs excluded; a group with no
-        collected values yields an EMPTY list (Spark semantics). Order
-        within a list is unspecified (as in Spark)."""
-        device = gids.device
-        assert not val.dtype.uses_offsets, \
-            "collect over string/list children: round 2"
-        keep = val.validity if val.validity is not None else \
-            torch.ones(len(val), dtype=torch.bool, device=device)
-        if dedupe:
-            base = key_cols if key_cols else [Column(dtypes.int64, gids)]
-            _, d_reps = ops.group_ids(base + [val])
-            sel = torch.zeros(len(val), dtype=torch.bool, device=device)
-            sel[d_reps] = True
-            keep = keep & sel
-        idx = torch.nonzero(keep, as_tuple=False).flatten()
-        g = gids[idx]
-        order = torch.argsort(g, stable=True)
-        rows = idx[order]
-        lens = torch.bincount(g[order], minlength=ngroups)
-        offsets = torch.zeros(ngroups + 1, dtype=torch.int64, device=device)
-        torch.cumsum(lens, 0, out=offsets[1:])
-        return Column(dtypes.list_of(val.dtype), val.data[rows], None,
-                      offsets.to(torch.int64))
-
-    def _finalize_agg(self, agg: AggFunc, vdt: DataType, acc, cnt: torch.Tensor,
-                      widen: bool = True) -> Column:
-        if agg.fn in ("collect_list", "collect_set"):
-            return acc  # empty groups stay empty lists, not null
-        validity = compact_validity(cnt > 0)
-        if isinstance(acc, Column):
-            v = acc.validity
-            if validity is not None:
-                v = validity if v is None else (v & validity)
-            return Column(acc.dtype, acc.data, v, acc.offsets)
-        if agg.fn == "avg":
-            if vdt.code == dtypes.DECIMAL64:
-                # Spark: avg(decimal(p,s)) -> decimal(p+4, s+4), HALF_UP;
-                # exact integer long division (advisor finding r1)
-                cnt_ = cnt.clamp(min=1)
-                sign = torch.sign(acc)
-                a = acc.abs()
-                q = torch.div(a, cnt_, rounding_mode="floor")
-                r = a - q * cnt_
-                frac = torch.div(r * 20000 + cnt_, cnt_ * 2,
-                                 rounding_mode="floor")
-                data = sign * (q * 10000 + frac)
-                out_dt = dtypes.decimal64(min(vdt.precision + 4, 18),
-                                          vdt.scale + 4)
-                return Column(out_dt, data, validity)
-            data = acc.to(torch.float64) / cnt.clamp(min=1).to(torch.float64)
-            return Column(dtypes.float64, data, validity)
-        # widen=False: vdt is ALREADY the state dtype (final mode) — a
-        # second _state_dtype pass would double-promote sum(decimal)
-        out_dt = self._state_dtype(agg, vdt) if widen else vdt
-        return Column(out_dt, acc, validity)
 
     # ------------------------------------------------------------ hash join
     def _exec_HashJoin(self, node: P.HashJoin) -> List[RecordBatch]:
@@ -2182,16 +1612,9 @@ class Executor:
         """Python UDAF: device grouping, host per-group callback."""
         b = _concat(self.execute(node.child))
         device = b.device
-        n = b.num_rows
         key_cols = [a.expr.eval(b) for a in node.keys]
-        if key_cols:
-            gids, reps = ops.group_ids(key_cols)
-            ngroups = int(reps.numel())
-            out_keys = [c.gather(reps) for c in key_cols]
-        else:
-            gids = torch.zeros(n, dtype=torch.int64, device=device)
-            ngroups = 1
-            out_keys = []
+        # keyless: always one group, the callback sees an empty input too
+        gids, ngroups, out_keys = group_rows(key_cols, b.num_rows, device)
         in_vals = [e.eval(b).to("cpu").to_pylist() for e in node.inputs]
         gl = gids.to("cpu").tolist()
         buckets: List[List[int]] = [[] for _ in range(ngroups)]

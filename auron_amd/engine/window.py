@@ -13,6 +13,8 @@ from ..column import Column, RecordBatch, adjacent_equal, compact_validity
 from ..exprs import AggFunc, Col, Literal, WindowFunc, _cast_col, \
     dec128_to_float64
 from ..plan import nodes as P
+from .agg import _finalize_agg, _state_dtype, _sum128_scatter, \
+    _sum_needs_128, _sum_split_128
 
 
 class _Peers:
@@ -407,16 +409,16 @@ def _running_aggregate(w: _Window, fn: str, val: Column) -> Column:
 
 
 def _aggregate(w: _Window, wf: WindowFunc, name: str) -> Column:
-    ex, node, L, fn = w.ex, w.node, w.lay, wf.fn
+    node, L, fn = w.node, w.lay, wf.fn
     val = wf.arg.eval(L.sb)
     wide = val.dtype.code == dtypes.DECIMAL128
-    if wide or (fn == "sum" and ex._sum_needs_128(val.dtype)):
+    if wide or (fn == "sum" and _sum_needs_128(val.dtype)):
         if fn == "sum" and not (node.order_by and L.n):
             # whole-partition sum promoted to decimal128:
             # exact limb accumulation (q12/q20/q98 ratios)
-            scatter = ex._sum128_scatter if wide else ex._sum_split_128
+            scatter = _sum128_scatter if wide else _sum_split_128
             data, cnt = scatter(L.seg, max(L.nseg, 1), val)
-            out_dt = val.dtype if wide else ex._state_dtype(
+            out_dt = val.dtype if wide else _state_dtype(
                 AggFunc("sum", None, name=name), val.dtype)
             return Column(out_dt, data,
                           compact_validity(cnt > 0)).gather(L.seg)
@@ -448,7 +450,7 @@ def _aggregate(w: _Window, wf: WindowFunc, name: str) -> Column:
     # value: MIN skips NaN unless all are NaN), whereas the frame and running
     # paths above keep "NaN propagates" into both MIN and MAX
     acc, cnt = ops.agg_scatter(L.seg, max(L.nseg, 1), val, fn)
-    return ex._finalize_agg(AggFunc(fn, None, name=name), val.dtype, acc,
+    return _finalize_agg(AggFunc(fn, None, name=name), val.dtype, acc,
                             cnt).gather(L.seg)
 
 
